@@ -13,6 +13,9 @@ count is not a multiple of N is dealt batch by batch; every round of N recording
 [3750, 13] logit blocks to rank 0, with sizes known on the host (no count exchange, no host synchronisation
 inside the timed region).  `python bench.py --gpus N` starts its own N child ranks (torch.distributed.run) when
 it is not already running under one.  Rank 0 prints ONE JSON line.
+
+`--dump-outputs DIR` (one GPU) also writes the logits the last timed step handed its callers to DIR/logits.npy; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -377,6 +380,29 @@ def file_batches(hop: int):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, results, windows_per_file: int, n_classes: int) -> dict:
+    """--dump-outputs: what each recording of the last timed step handed its caller (DeviceResult.numpy(): the range verdict
+    waited for, the rows repeated in exact f32 when it was raised), as logits.npy [R, windows, classes] float32 and
+    recording.npy [R] float64 (the recording's number in the timed region).  Beyond 64 MB, a seeded sample of the recordings."""
+    import numpy as np
+    by_rec = {}
+    for rec, batch, res in results:
+        by_rec.setdefault(rec, {})[batch] = res
+    recs = sorted(by_rec)
+    keep = DUMP_LIMIT_BYTES // (windows_per_file * n_classes * 4 + 8)
+    if keep < len(recs):
+        recs = [recs[i] for i in sorted(np.random.default_rng(0).choice(len(recs), size=keep, replace=False))]
+    logits = np.stack([np.concatenate([by_rec[r][b].numpy() for b in sorted(by_rec[r])]) for r in recs]).astype(np.float32)
+    assert logits.shape == (len(recs), windows_per_file, n_classes), logits.shape
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "logits.npy"), logits)
+    np.save(os.path.join(path, "recording.npy"), np.asarray(recs, dtype=np.float64))
+    return {"logits": list(logits.shape), "recording": [len(recs)]}
+
+
 def cpu_baseline(engine, hop: int, step: int, windows: int):
     """The oracle timed on this box's host cores (checker + reported baseline, never the product).
     The sample is cut into the workload's own 1024-window chunks on both sides."""
@@ -562,7 +588,14 @@ def main() -> int:
     ap.add_argument("--group-windows", type=int, default=0, help="windows per CNN pass (0 = library default)")
     ap.add_argument("--files-per-step", type=int, default=FILES_PER_STEP,
                     help="recordings per step (50: --steps 20 is config 4's 1000 x 1 h; profiling runs use fewer)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits the last timed step handed its callers to DIR/*.npy "
+                         "(float32 / float64, at most 64 MB: a seeded sample of the recordings beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return self_launch(args.gpus)
@@ -645,17 +678,24 @@ def main() -> int:
     # the round) into the first spare row behind its block; rank 0 adds them up on the communication stream
     seen = torch.zeros((world, 2), dtype=torch.float64, device="cpu" if rehearsal else device) if world > 1 and rank == 0 else None
 
-    def run_files(n_steps: int, use_streams: bool = True):
+    def run_files(n_steps: int, use_streams: bool = True, last_step=None):
         """n_steps x 50 recordings through this rank's share of the rounds (see the module docstring).  Once per step (50
         recordings) one batch's result is read back on the host through DeviceResult.numpy() - the path the reference's
         writer takes (src/write/worker.py:69): the range verdict of its launch set is waited for and looked at, the rows
-        cross PCIe - so the verdict path is inside the timed region."""
+        cross PCIe - so the verdict path is inside the timed region.
+        `last_step` (--dump-outputs): {"blocks": {round: [rows, C] tensor}, "results": []}; the results of the last step's
+        recordings are appended to "results" as (recording, batch, DeviceResult), and a round found in "blocks" writes its
+        rows there instead of into the ring, which later rounds overwrite."""
         rounds = sharding.plan_rounds(n_steps * files_per_step, batch_windows, world)
         per_step = max(1, len(rounds) // max(n_steps, 1))
+        first_kept = (n_steps - 1) * files_per_step
         for ri, rnd in enumerate(rounds):
             local, gath, reusable = buffers(rnd.rows)
             slot = issued[0] % RING
             issued[0] += 1
+            block = local[slot]
+            if last_step is not None and ri in last_step["blocks"]:
+                block = last_step["blocks"][ri]
             mine = rnd.units[rank]
             used = set()
             probe = None
@@ -669,9 +709,11 @@ def main() -> int:
                 first, n = batches[u.batch]
                 with torch.cuda.stream(s):
                     res = engines[j].predict(files[u.file % len(files)][first:first + n], framehop_s,
-                                             out=local[slot][at:at + u.windows])
+                                             out=block[at:at + u.windows])
                 if probe is None:
                     probe = res
+                if last_step is not None and u.file >= first_kept:
+                    last_step["results"].append((u.file, u.batch, res))
             if world > 1:
                 # the marker row is written in EVERY round, also by a rank that has no units in it (windows = 0): a reused
                 # ring slot would otherwise hand rank 0 the marker of the slot's previous round a second time
@@ -680,8 +722,8 @@ def main() -> int:
                     mark_stream.wait_event(reusable[slot])
                 used.add(streams.index(mark_stream))
                 with torch.cuda.stream(mark_stream):
-                    local[slot][rnd.rows, 0] = float(rank + 1)
-                    local[slot][rnd.rows, 1] = float(sum(u.windows for u in mine))
+                    block[rnd.rows, 0] = float(rank + 1)
+                    block[rnd.rows, 1] = float(sum(u.windows for u in mine))
             if probe is not None and ri % per_step == per_step - 1:
                 rows = probe.numpy()                       # waits for that launch set's verdict, repeats in f32 if raised
                 read_back["batches"] += 1
@@ -693,9 +735,9 @@ def main() -> int:
                 with torch.cuda.stream(comm_stream):
                     nrow = rnd.rows + sharding.ROW_ALIGN
                     if rehearsal:
-                        sharding.gather_round(local[slot].cpu(), nrow, dst=0, out=gath[slot] if gath else None)
+                        sharding.gather_round(block.cpu(), nrow, dst=0, out=gath[slot] if gath else None)
                     else:
-                        sharding.gather_round(local[slot], nrow, dst=0, out=gath[slot] if gath else None)
+                        sharding.gather_round(block, nrow, dst=0, out=gath[slot] if gath else None)
                     if seen is not None:                   # per sending rank: rounds it took part in, windows it delivered
                         mark = gath[slot][:, rnd.rows, :2].to(torch.float64)
                         ok = (mark[:, 0] == torch.arange(1, world + 1, dtype=torch.float64, device=mark.device))
@@ -710,10 +752,10 @@ def main() -> int:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_region(steps: int, use_streams: bool = True) -> float:
+    def timed_region(steps: int, use_streams: bool = True, last_step=None) -> float:
         fence()
         t0 = time.perf_counter()
-        run_files(steps, use_streams)
+        run_files(steps, use_streams, last_step)
         fence()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -724,8 +766,20 @@ def main() -> int:
 
     if rank == 0:
         log(f"warm-up {args.warmup} steps, then {args.steps} timed steps ({files_per_step} x 1 h recordings each) over {world} GPU(s)")
-    run_files(max(args.warmup, 0))
+    # --dump-outputs: the timed region keeps its last step's results alive until it ends, and every result holds a range
+    # verdict (a pinned word + event) out of the engine's pool; the warm-up's last step is held the same way, so that the
+    # pool has grown to that size before the timed region starts and allocates nothing inside it
+    dump = args.dump_outputs is not None
+    run_files(max(args.warmup, 0), last_step={"blocks": {}, "results": []} if dump else None)
     fence()
+    last_step = None
+    if dump:
+        first_kept = (args.steps - 1) * files_per_step
+        last_step = {"results": [], "blocks": {
+            ri: torch.zeros((rnd.rows + sharding.ROW_ALIGN, n_classes), dtype=torch.float32, device=device)
+            for ri, rnd in enumerate(sharding.plan_rounds(args.steps * files_per_step, batch_windows, world))
+            if any(u.file >= first_kept for units in rnd.units for u in units)}}
+        torch.cuda.synchronize()
 
     # region 1: the number reported as `value` — nothing but the hot path (and, for N > 1, the gathers)
     for e in engines:
@@ -737,8 +791,13 @@ def main() -> int:
         if seen is not None:
             seen.zero_()           # ... so the count below is the timed region's alone
     with PowerWatch(torch, dev_index) as watch:
-        elapsed = timed_region(args.steps)
+        elapsed = timed_region(args.steps, last_step=last_step)
     timed_read_back = dict(read_back, exact_f32_repeats=sum(e.overflow_reruns for e in engines) - reruns0)
+    dumped = None
+    if dump:
+        dumped = dump_outputs(args.dump_outputs, last_step["results"], windows_per_file, n_classes)
+        last_step = None
+        log(f"last timed step's outputs -> {args.dump_outputs}: {dumped}")
     ranks_seen = None
     if seen is not None:
         ranks_seen = [{"rank": r, "rounds": int(seen[r, 0].item()), "windows": int(seen[r, 1].item())} for r in range(world)]
@@ -837,6 +896,8 @@ def main() -> int:
         }
         if args.pointwise_mode is not None:
             out["mode_override"] = args.pointwise_mode
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if ranks_seen is not None:
             out["ranks_seen"] = ranks_seen
             out["ranks_seen_note"] = ("counted on rank 0 from the gathered blocks of the timed region: rounds in which the block "
