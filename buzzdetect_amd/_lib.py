@@ -97,6 +97,42 @@ PROTOTYPES = {
     "bd_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
 }
 
+FLAC_ABI_VERSION = 1
+
+
+class bd_flac_streaminfo(C.Structure):
+    _fields_ = [("min_blocksize", C.c_int32), ("max_blocksize", C.c_int32), ("sample_rate", C.c_int32),
+                ("channels", C.c_int32), ("bits_per_sample", C.c_int32), ("reserved", C.c_int32),
+                ("total_samples", C.c_int64)]
+
+
+class bd_flac_frame_header(C.Structure):
+    _fields_ = [("number", C.c_int64), ("first_sample", C.c_int64), ("blocksize", C.c_int32), ("sample_rate", C.c_int32),
+                ("channel_assignment", C.c_int32), ("channels", C.c_int32), ("bits_per_sample", C.c_int32),
+                ("variable", C.c_int32), ("header_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class bd_flac_status(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("stop_offset", C.c_int64), ("first_sample", C.c_int64), ("end_sample", C.c_int64),
+                ("reason", C.c_int32), ("frames", C.c_int32)]
+
+
+FLAC_STOP_NAMES = {0: "end", 1: "crc16", 2: "bad_subframe", 3: "lost_sync", 4: "truncated", 5: "overflow"}
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_flac.h
+FLAC_PROTOTYPES = {
+    "bd_flac_abi_version": (C.c_int, []),
+    "bd_flac_crc8": (C.c_uint32, [C.c_void_p, C.c_int64]),
+    "bd_flac_crc16": (C.c_uint32, [C.c_void_p, C.c_int64]),
+    "bd_flac_parse_frame_header": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(bd_flac_streaminfo),
+                                             C.POINTER(bd_flac_frame_header)]),
+    "bd_flac_decode_host": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(bd_flac_streaminfo), C.c_int64, C.c_int64, C.c_void_p,
+                                      C.POINTER(bd_flac_status)]),
+    "bd_flac_workspace_bytes": (C.c_int64, [C.POINTER(bd_flac_streaminfo), C.c_int64, C.c_int64]),
+    "bd_flac_decode": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(bd_flac_streaminfo), C.c_int64, C.c_int64, C.c_void_p,
+                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -128,12 +164,14 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         except (RuntimeError, OSError, subprocess.CalledProcessError) as exc:
             raise RuntimeError(f"{path} is older than its sources and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
     if lib.bd_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.bd_abi_version()} != {ABI_VERSION}; rebuild")
+    if lib.bd_flac_abi_version() != FLAC_ABI_VERSION:
+        raise RuntimeError(f"{path}: FLAC ABI version {lib.bd_flac_abi_version()} != {FLAC_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

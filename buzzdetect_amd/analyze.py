@@ -11,8 +11,9 @@ surrounds the hot path:
     output-folder manifest                                     src/pipeline/manifest.py:62-85
     streamers -> bounded queue -> analyzers -> writer          src/pipeline/coordination.py:26-194  (buzzdetect_amd/pipeline.py)
 
-One process per GPU walks its share of the recordings (round-robin, ``sharding.shard_indices``).  Compressed formats
-are not decoded here (the reference uses libsndfile / PyAV on the CPU, out of scope): inputs are uncompressed ``.wav``.
+One process per GPU walks its share of the recordings (round-robin, ``sharding.shard_indices``).  Inputs are ``.wav``
+(uncompressed) and ``.flac``, whose frames are decoded on the device (flacio.py, csrc/flac.hip); the formats the
+reference reads through PyAV on the CPU (MP3, MP4, ...) are out of scope.
 """
 from __future__ import annotations
 
@@ -26,7 +27,7 @@ from .pipeline import log as _log
 from .wavio import WavTrack  # noqa: F401  (re-exported: the streamer's reader)
 
 AnalyzeReport = Report
-EXTENSIONS = (".wav",)
+EXTENSIONS = (".wav", ".flac")
 STREAMERS_PER_ANALYZER = 3        # the reference runs 8 decoding streamers per GPU analyzer (coordination.py:129-138);
                                   # reading uncompressed PCM (~8 GB/s per thread) needs fewer
 
@@ -55,7 +56,7 @@ def analyze(modelname: str = "model_general_v3", classes_out="all", precision: O
             gather_logits: bool = False, analyzers_cpu: int = 0, stream_buffer_depth: Optional[int] = None,
             verbosity_print: Optional[str] = None, verbosity_log: Optional[str] = None, log_progress: bool = False,
             event_stopanalysis=None) -> AnalyzeReport:
-    """Analyse every ``.wav`` under ``dir_audio``; write ``<ident>_buzzdetect.csv`` under ``dir_out``.
+    """Analyse every ``.wav`` and ``.flac`` under ``dir_audio``; write ``<ident>_buzzdetect.csv`` under ``dir_out``.
 
     ``classes_out`` / ``precision`` choose activations vs detections exactly as in the reference;
     ``rank`` / ``world_size`` default to the torch.distributed environment (one process per GPU);
@@ -213,6 +214,7 @@ def gather_plan(todo, dir_out: str, hop: int, step: int, chunklength: float) -> 
     everywhere or the collectives mismatch."""
     from . import _lib
     from .pipeline import log
+    from .flacio import open_track
     from .wavio import WavFormatError
     lib = _lib.load()
     plan = []
@@ -221,7 +223,7 @@ def gather_plan(todo, dir_out: str, hop: int, step: int, chunklength: float) -> 
         if rf.complete or os.path.getsize(path) < FILE_SIZE_MINIMUM:
             continue
         try:
-            track = WavTrack(path)
+            track = open_track(path)
         except (WavFormatError, OSError) as exc:
             log.warning(f"planner: {exc}; skipping")
             continue

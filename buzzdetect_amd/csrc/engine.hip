@@ -295,6 +295,10 @@ int calibrate_builtin(bd_engine* e);
 
 }  // namespace
 
+namespace bd {
+void set_error(const std::string& msg) { g_error = msg; }
+}  // namespace bd
+
 extern "C" {
 
 int bd_abi_version(void) { return BD_ABI_VERSION; }

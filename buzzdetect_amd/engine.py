@@ -9,6 +9,7 @@ Replaces, behind the reference's plugin surface (see ``buzzdetect_amd/dropin``):
 from __future__ import annotations
 
 import ctypes as C
+import os
 import threading
 from typing import List, Optional, Sequence, Tuple
 
@@ -439,6 +440,33 @@ class HipEngine:
                           out.data_ptr(), self._stream().cuda_stream))
         t.record_stream(self._stream())
         return out
+
+    def read_flac(self, path: str, start: int = 0, frames: Optional[int] = None) -> torch.Tensor:
+        """Samples [start, start + frames) of a FLAC file (default: to its end) decoded on the device: float32
+        [frames, channels], as soundfile.read(dtype="float32") gives them.  A frame that fails its checks ends the audio
+        early (the tensor is shorter), as a file cut short does."""
+        from .flacio import FlacDecoder, FlacTrack
+        track = FlacTrack(path)
+        try:
+            start = min(max(int(start), 0), track.frames)
+            n = track.frames - start if frames is None else min(int(frames), track.frames - start)
+            out = torch.empty((max(n, 0), track.channels), dtype=torch.int16 if track.is_s16 else torch.float32, device=self.device)
+            if n <= 0:
+                return out.to(torch.float32)
+            off, end = track.byte_range(start, n)
+            stream = self._stream()
+            dec = FlacDecoder(torch, self.device)
+            comp = dec.staging(end - off)
+            data = np.frombuffer(os.pread(track.fd, end - off, off), np.uint8)
+            comp[: data.size].copy_(torch.from_numpy(data.copy()), non_blocking=False)
+            with torch.cuda.device(self.device):
+                dec.decode(track, data.size, start, n, out.data_ptr(), stream)
+            stream.synchronize()
+            got = int(dec.result().samples)
+        finally:
+            track.close()
+        out = out[:got]
+        return out.to(torch.float32) / 32768.0 if track.is_s16 else out
 
     # ------------------------------------------------------------------ hot path
     def frontend(self, samples, hop: int) -> torch.Tensor:
