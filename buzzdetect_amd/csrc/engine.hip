@@ -7,6 +7,8 @@
 #include <unistd.h>
 #include <memory>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "bd_internal.h"
@@ -54,13 +56,7 @@ struct bd_engine {
     int group_windows = kDefaultGroup;
     int pointwise_mode = 1;           // 0 = exact f32 MFMA, 1 = split-f16 MFMA, 2 = plain f16 MFMA
     unsigned* d_range_flag = nullptr; // sticky: an activation exceeded the f16 range in mode 1 / 2 (bd_range_flag)
-    // bd_set_fusion (round 6: per layer group the default, one kernel per op, and at most ONE previous form):
-    bool fuse_stem = true;            // layers 1-3 as one kernel (stem != 0)
-    bool stem_reg = true;             // ... with the layer-2 tile handed over in registers (stemreg.hip; stem = 3, default); 5: through LDS
-    bool fuse_sep = true;             // layers 4-14 on the fused kernels (separable != 0)
-    bool chip_mid = true;             // pointwise 5 -> layer 6 -> depthwise 7 -> pointwise 7 as one on-chip launch (sepmid.hip);
-                                      // separable = 10: the four kernels of round 4.  (Layers 8-12 + depthwise 13 as one on-chip launch
-                                      // - sepchip.hip - and layers 13 / 14 on septail.hip's kernel have no other fused form left.)
+    int stem = 3, separable = 1;      // bd_set_fusion codes (pass_f16 / pass_f32 read them)
     float* d_pool = nullptr;          // one allocation for every folded tensor
     bd::FeTables* d_tables = nullptr;
     // operand scaling of the f16 modes (bd_internal.h, SepLayer): host copies of what the scaled tensors are made from
@@ -100,28 +96,18 @@ struct bd_engine {
 namespace {
 
 // Records the marker event of one launch (or, with slot < 0, the head marker of a call).
-struct Scope {
-    bd_engine* e;
-    hipStream_t s;
-    int slot;
-    bool on;
-    static void mark(bd_engine* e, hipStream_t s, int slot) {
-        Event2 ev;
-        if (!e->free_events.empty()) {
-            ev = e->free_events.back();
-            e->free_events.pop_back();
-        } else if (hipEventCreate(&ev.ev) != hipSuccess) {
-            return;
-        }
-        ev.slot = slot;
-        (void)hipEventRecord(ev.ev, s);
-        e->pending.push_back(ev);
+void mark(bd_engine* e, hipStream_t s, int slot) {
+    Event2 ev;
+    if (!e->free_events.empty()) {
+        ev = e->free_events.back();
+        e->free_events.pop_back();
+    } else if (hipEventCreate(&ev.ev) != hipSuccess) {
+        return;
     }
-    Scope(bd_engine* e_, hipStream_t s_, int slot_) : e(e_), s(s_), slot(slot_), on(e_->profiling) {}
-    ~Scope() {
-        if (on) mark(e, s, slot);
-    }
-};
+    ev.slot = slot;
+    (void)hipEventRecord(ev.ev, s);
+    e->pending.push_back(ev);
+}
 
 // Developer build (-DBD_KERNEL_TRACE) only: BD_REPEAT_SLOT=<profile slot> BD_REPEAT_N=<n> launches that slot's kernel n times
 // per pass (same operands: the kernels are idempotent), so that one kernel dominates a run - its sustained clock and the
@@ -132,10 +118,21 @@ static int repeat_of(int slot) {
     static const int n = getenv("BD_REPEAT_N") ? atoi(getenv("BD_REPEAT_N")) : 1;
     return slot == want ? n : 1;
 }
-#define BD_REPEAT_EXTRA(slot) for (int rep_ = repeat_of(slot) - 1; rep_ > 0; --rep_)
-#else
-#define BD_REPEAT_EXTRA(slot) if (false)
 #endif
+
+// One launch timed in profile `slot`: fn() launches the kernel (a launcher that returns false or 0 declined: nothing ran,
+// nothing is recorded and launch returns false), the developer build repeats it, and with profiling on the slot's marker
+// event follows it.
+template <class F>
+bool launch(bd_engine* e, hipStream_t s, int slot, F fn) {
+    if constexpr (std::is_void_v<decltype(fn())>) fn();
+    else if (!fn()) return false;
+#ifdef BD_KERNEL_TRACE
+    for (int r = repeat_of(slot); r > 1; --r) (void)fn();
+#endif
+    if (e->profiling) mark(e, s, slot);
+    return true;
+}
 
 // ---- index arithmetic: embedders/yamnet/features.py:82-108, :42-46, :65-76 ----
 int64_t padded_length(int64_t n, int32_t hop) {
@@ -632,11 +629,9 @@ int bd_frontend(bd_handle h, const float* pcm_dev, int64_t n_samples, int32_t ho
     const int rc = geometry(n_samples, hop_samples, 0, &g);
     if (rc < 0) return rc;
     BD_HIP(hipSetDevice(h->device));
-    if (h->profiling) Scope::mark(h, (hipStream_t)stream, -1);
-    {
-        Scope sc(h, (hipStream_t)stream, 0);
-        bd::launch_logmel(pcm_dev, n_samples, g.n_frames, logmel_dev, h->d_tables, (hipStream_t)stream);
-    }
+    if (h->profiling) mark(h, (hipStream_t)stream, -1);
+    launch(h, (hipStream_t)stream, 0,
+           [&] { bd::launch_logmel(pcm_dev, n_samples, g.n_frames, logmel_dev, h->d_tables, (hipStream_t)stream); });
     BD_HIP(hipGetLastError());
     return BD_OK;
 }
@@ -850,6 +845,167 @@ int64_t batch_workspace(const bd_engine* e, const BatchPlan& p) {
            align_up(group * kFloatsB * 4, 256) + 256;
 }
 
+// One group of windows on its way through the CNN.  Of the two activation buffers, `a` (98 304 floats per window) holds the
+// latest conv / 1x1 output and `b` (49 152) the depthwise side; where a fused launch leaves them the other way round, the
+// pass swaps them right behind it.
+struct Group {
+    bd_engine* e;
+    const bd::SepLayer* sep;       // this call's view of the layers (sep[l] = layer l + 2)
+    hipStream_t stream;
+    const float* logmel;           // the batch's log-mel frames; map and step take windows to them
+    const bd::WindowMap* map;
+    int step;
+    int w0, gw;                    // the group's first window and its number of windows
+    float* a;
+    float* b;
+    float* emb;                    // the group's rows of the outputs, or null
+    float* logits;
+    template <class F>
+    bool launch(int slot, F fn) { return ::launch(e, stream, slot, fn); }
+};
+
+// conv1 (layer 1): log-mel patches -> a
+void conv1(Group& g) {
+    g.launch(1, [&] { bd::launch_conv1(g.logmel, g.step, *g.map, g.w0, g.gw, g.e->conv1_w, g.e->conv1_b, g.a, g.stream); });
+}
+
+// Layers 1-3 as one kernel: log-mel patches -> the layer-3 output in a, timed in the slot of pointwise 3 (slots 1-4 stay empty)
+void stem(Group& g, decltype(&bd::launch_stem4) fn) {
+    g.launch(5, [&] { fn(g.logmel, g.step, *g.map, g.w0, g.gw, g.e->conv1_w, g.e->conv1_b, g.sep[0], g.sep[1], g.a, g.stream); });
+}
+
+// The 1x1 convolution of layer index l: b -> a
+void pointwise(Group& g, int l) {
+    const bd::SepLayer& L = g.sep[l];
+    g.launch(3 + 2 * l, [&] { bd::launch_pointwise(g.b, g.a, (int64_t)g.gw * L.h_out * L.w_out, L, g.stream); });
+}
+
+// The dense head on the embeddings a tail kernel pooled
+int head(Group& g, const float* pooled) {
+    if (g.logits)
+        g.launch(28, [&] { bd::launch_head(pooled, g.gw, g.e->head_wt, g.e->head_b, g.e->n_classes, g.logits, g.stream); });
+    return BD_OK;
+}
+
+// One kernel per op from layer index `from` (layer from + 2) on; dw_done: b already holds that layer's depthwise output.  In
+// the f16 modes with separable != 0, a stride-1 layer followed by a stride-2 one runs with the next depthwise in its epilogue
+// (launch_separable_fused_next_dw: a -> b) unless stop_stage lies between.  stop_stage >= 0: stop once that stage is in place
+// (an even stage, a conv / 1x1 output, in a; an odd one, a depthwise output, in b); otherwise end the group with pool + head.
+int walk_layers(Group& g, int from, bool dw_done, int stop_stage) {
+    const bd::SepLayer* sep = g.sep;
+    const bool fuse_next_dw = sep[0].pw_mode != 0 && g.e->separable != 0;
+    for (int l = from; l < 13; ++l) {
+        if (stop_stage == 2 * l) return BD_OK;
+        const bd::SepLayer& L = sep[l];
+        if (fuse_next_dw && !dw_done && l + 1 < 13 && (stop_stage < 0 || stop_stage >= 2 * l + 4) &&
+            g.launch(3 + 2 * l, [&] { return bd::launch_separable_fused_next_dw(g.a, g.b, g.gw, L, sep[l + 1], g.stream); })) {
+            dw_done = true;
+            continue;
+        }
+        if (!dw_done) g.launch(2 + 2 * l, [&] { bd::launch_depthwise(g.a, g.b, g.gw, L, g.stream); });
+        if (stop_stage == 2 * l + 1) return BD_OK;
+        pointwise(g, l);
+        dw_done = false;
+    }
+    if (stop_stage < 0)
+        g.launch(28, [&] {
+            bd::launch_pool_head(g.a, g.gw, g.e->head_wt, g.e->head_b, g.e->n_classes, g.emb, g.logits, g.stream);
+        });
+    return BD_OK;
+}
+
+// The split-f16 launch set (modes 1 and 2) of one group.  A fused launcher that declines (shape guard, window limit) hands
+// the rest of the group to walk_layers.
+int pass_f16(Group& g) {
+    const bd_engine* e = g.e;
+    const bd::SepLayer* sep = g.sep;
+    if (e->stem != 0) {
+        // the layer-2 tile handed to depthwise 3 in registers (stemreg.hip), or through LDS (stem3_kernel, stem 5)
+        stem(g, e->stem == 3 ? bd::launch_stem_reg : bd::launch_stem4);
+    } else {
+        conv1(g);
+        walk_layers(g, 0, false, 4);
+    }
+    if (e->separable == 0) return walk_layers(g, 2, false, -1);
+    // layer 4 + depthwise 5, a window per workgroup (l4_window_kernel): a -> b
+    if (!g.launch(7, [&] { return bd::launch_separable_fused_next_dw(g.a, g.b, g.gw, sep[2], sep[3], g.stream); }))
+        return walk_layers(g, 2, false, -1);
+    // pointwise 5 -> layer 6 -> depthwise 7 -> pointwise 7 as one on-chip launch (sepmid.hip): b -> a.  Separable 10, or the
+    // launcher declined: pointwise 5, layer 6 + depthwise 7 (sep_ws_kernel<1, 0>: a -> b), pointwise 7
+    if (!(e->separable == 1 &&
+          g.launch(13, [&] { return bd::launch_separable_mid(g.b, g.a, g.gw, sep[3], sep[4], sep[5], g.stream); }))) {
+        pointwise(g, 3);
+        if (!g.launch(11, [&] { return bd::launch_separable_fused_next_dw(g.a, g.b, g.gw, sep[4], sep[5], g.stream); }))
+            return walk_layers(g, 4, false, -1);
+        pointwise(g, 5);
+    }
+    // layers 8-12 + depthwise 13 as one on-chip launch (sepchip.hip): a -> b, as the f16 hi / lo planes septail.hip reads
+    // when its kernel can follow (32-bit offsets: up to 2^18 windows), else as f32 for one kernel per op
+    const bool planes = g.gw <= (1 << 18) && bd::tail_supported(sep[11], sep[12]);
+    if (!g.launch(23, [&] { return bd::launch_separable_run_next_dw(g.a, g.b, g.gw, &sep[6], 7, g.stream, planes); }))
+        return walk_layers(g, 6, false, -1);
+    if (!planes) return walk_layers(g, 11, true, -1);
+    // pointwise 13 + depthwise 14 (planes b -> planes a), pointwise 14 + average pool (-> [windows][1024]) on septail.hip
+    float* const pooled = g.emb ? g.emb : g.b;
+    if (!g.launch(25, [&] { return bd::launch_tail_pw13_dw14(g.b, g.a, g.gw, sep[11], sep[12], g.stream); }) ||
+        !g.launch(27, [&] { return bd::launch_tail_pw14_pool(g.a, pooled, g.gw, sep[12], g.stream); }))
+        return fail(BD_EHIP, "septail.hip declined the planes of the on-chip run");
+    return head(g, pooled);
+}
+
+// The exact-f32 launch set (mode 0) of one group, behind the fused stem (stem != 0).  Every kernel is bit-identical to the
+// ones it replaces.  A fused launcher that declines hands the rest of the group to walk_layers.
+int pass_f32(Group& g) {
+    const bd_engine* e = g.e;
+    const bd::SepLayer* sep = g.sep;
+    // layers 1-3 on v_mfma_f32_32x32x2_f32 with the layer-2 tile handed over in registers (stemregf32.hip; stem 5 too)
+    stem(g, bd::launch_stem_reg_f32);
+    if (e->separable == 0) return walk_layers(g, 2, false, -1);
+    // layer 4 + depthwise 5, the layer-4 tile handed over in registers (l4regf32.hip): a -> b
+    if (!g.launch(7, [&] { return bd::launch_l4_reg_f32(g.a, g.b, g.gw, sep[2], sep[3], g.stream); }))
+        return walk_layers(g, 2, false, -1);
+    // pointwise 5 -> layer 6 -> layer 7 as one launch (sepmidf32.hip): b -> a.  Separable 10, or the launcher declined: the 1x1
+    // convolutions of layers 5, 6 and 7, each with the next depthwise in its epilogue (b -> a, then swapped: b holds it)
+    bool dw8_done = false;
+    if (!(e->separable == 1 &&
+          g.launch(13, [&] { return bd::launch_separable_mid_f32(g.b, g.a, g.gw, sep[3], sep[4], sep[5], g.stream); }))) {
+        for (int l = 3; l < 6; ++l) {
+            if (!g.launch(3 + 2 * l, [&] { return bd::launch_pointwise_next_dw_f32(g.b, g.a, g.gw, sep[l], sep[l + 1], g.stream); }))
+                return walk_layers(g, l, true, -1);
+            std::swap(g.a, g.b);
+        }
+        dw8_done = true;
+    }
+    // layers 8-12 + depthwise 13 as one launch whose tiles stay on the CU (sepchipf32.hip): the layer-7 output in a (or the
+    // depthwise-8 output in b) -> the depthwise-13 output in the other buffer
+    if (!g.launch(23, [&] {
+            return dw8_done ? bd::launch_separable_chip_f32(g.b, g.a, g.gw, &sep[6], 5, g.stream, &sep[11], true)
+                            : bd::launch_separable_chip_f32(g.a, g.b, g.gw, &sep[6], 5, g.stream, &sep[11], false);
+        }))
+        return walk_layers(g, 6, dw8_done, -1);
+    if (dw8_done) std::swap(g.a, g.b);
+    // pointwise 13 + depthwise 14 (b -> a), pointwise 14 + average pool (-> [windows][1024]) on septail.hip (32-bit byte
+    // offsets: up to 2^17 windows)
+    if (g.gw > (1 << 17) || !bd::tail_f32_supported(sep[11], sep[12])) return walk_layers(g, 11, true, -1);
+    float* const pooled = g.emb ? g.emb : g.b;
+    if (!g.launch(25, [&] { return bd::launch_tail_f32(g.b, g.a, pooled, g.gw, sep[11], sep[12], g.stream, 0); }) ||
+        !g.launch(27, [&] { return bd::launch_tail_f32(g.b, g.a, pooled, g.gw, sep[11], sep[12], g.stream, 1); }))
+        return fail(BD_EHIP, "septail.hip declined the exact-f32 tail");
+    return head(g, pooled);
+}
+
+// Calibration, the stage taps and the exact-f32 mode with stem 0: one kernel per op from conv1 on.  An f16 tap at or behind
+// stage 4 keeps the fused stem (stemreg.hip only when the tap is its output, stem3_kernel otherwise, even with stem 3) and
+// the depthwise fusions of walk_layers.
+int pass_per_op(Group& g, int stop_stage) {
+    if (g.sep[0].pw_mode != 0 && g.e->stem != 0 && stop_stage >= 4) {
+        stem(g, g.e->stem == 3 && stop_stage == 4 ? bd::launch_stem_reg : bd::launch_stem4);
+        return walk_layers(g, 2, false, stop_stage);
+    }
+    conv1(g);
+    return walk_layers(g, 0, false, stop_stage);
+}
+
 // The launch plan of one batch of chunks.  stop_stage < 0: run everything; otherwise stop after that CNN
 // stage of the first group and copy it to tap_out.
 // chunk_pcm[c]: device pointer of chunk c (4-byte aligned; the packed entry points pass pcm + the samples before it).
@@ -893,260 +1049,42 @@ int run_chunks(bd_engine* e, const float* const* chunk_pcm, const int64_t* chunk
     }
     const int64_t need = batch_workspace(e, plan);
     if (!ws || ws_bytes < need) return fail(BD_EWORKSPACE, "workspace smaller than bd_workspace_bytes()");
-    struct { int64_t n_frames, n_windows; } g = {plan.total_frames, plan.total_windows};
-    if (stop_stage >= 0 && (tap_windows <= 0 || tap_windows > g.n_windows || tap_windows > e->group_windows))
+    const int64_t n_windows = plan.total_windows;
+    if (stop_stage >= 0 && (tap_windows <= 0 || tap_windows > n_windows || tap_windows > e->group_windows))
         return fail(BD_EINVAL, "bd_stage_tap: windows must be in 1..min(n_windows, group)");
-    BD_HIP(hipSetDevice(e->device));
 
-    const int64_t group = g.n_windows < e->group_windows ? g.n_windows : e->group_windows;
+    const int64_t group = n_windows < e->group_windows ? n_windows : e->group_windows;
     char* base = static_cast<char*>(ws);
-    float* logmel = reinterpret_cast<float*>(base);
-    float* const buf_a0 = reinterpret_cast<float*>(base + align_up(g.n_frames * BD_MEL_BANDS * 4, 256));
-    float* const buf_b0 = reinterpret_cast<float*>(reinterpret_cast<char*>(buf_a0) + align_up(group * kFloatsA * 4, 256));
+    float* const logmel = reinterpret_cast<float*>(base);
+    float* const buf_a = reinterpret_cast<float*>(base + align_up(plan.total_frames * BD_MEL_BANDS * 4, 256));
+    float* const buf_b = reinterpret_cast<float*>(reinterpret_cast<char*>(buf_a) + align_up(group * kFloatsA * 4, 256));
 
-    if (e->profiling) Scope::mark(e, stream, -1);
-    for (int c = 0; c < n_chunks; ++c) {       // one front-end launch per chunk: its padding is its own
-        Scope sc(e, stream, 0);
-        bd::launch_logmel(chunk_pcm[c], chunk_samples[c], plan.frames[c],
-                          logmel + (int64_t)plan.map.frame_base[c] * BD_MEL_BANDS, e->d_tables, stream);
-        BD_REPEAT_EXTRA(0)
+    if (e->profiling) mark(e, stream, -1);
+    for (int c = 0; c < n_chunks; ++c)        // one front-end launch per chunk: its padding is its own
+        launch(e, stream, 0, [&] {
             bd::launch_logmel(chunk_pcm[c], chunk_samples[c], plan.frames[c],
                               logmel + (int64_t)plan.map.frame_base[c] * BD_MEL_BANDS, e->d_tables, stream);
-    }
-    const float* const lm = logmel;
-    for (int64_t w0 = 0; w0 < g.n_windows; w0 += group) {
-        const int gw = stop_stage >= 0 ? tap_windows : (int)(g.n_windows - w0 < group ? g.n_windows - w0 : group);
-        // buf_a holds the latest conv/pointwise output, buf_b the scratch side; the fused separable
-        // layers swap the two (everything after layer 2 fits the smaller buffer), so start each pass
-        // from the sized assignment: A = 98 304 floats/window, B = 49 152
-        float* buf_a = buf_a0;
-        float* buf_b = buf_b0;
-        // layers 1-3 run as one fused kernel (split-f16 mode) unless a test taps inside them
-        const bool fuse_stem = e->fuse_stem && mode != 0 && (stop_stage < 0 || stop_stage >= 2);
-        const float* last = buf_a;
-        int64_t last_floats = 0;
-        bool stopped = false;
-        int first_layer = 0;
-        // (a tap inside layers 1-3 runs them one kernel per op)
-        const bool fuse_stem3 = fuse_stem && (stop_stage < 0 || stop_stage >= 4);
-        int skip_dw_layer = -1;      // loop index of a layer whose depthwise the previous kernel already applied
-        bool f32_l4 = false;         // exact-f32 mode: layer 4 + the depthwise of layer 5 as one kernel behind the f32 stem
-        if (fuse_stem3) {
-            {
-                Scope sc(e, stream, 5);      // timed in the slot of pointwise 3 (slots 1-4 stay empty)
-                const bool alt = mode != 0 && (stop_stage < 0 || stop_stage == 4);
-                auto stem_launch = [&]() {
-                    if (e->stem_reg && alt)
-                        bd::launch_stem_reg(lm, step, plan.map, (int)w0, gw, e->conv1_w, e->conv1_b, sep[0], sep[1], buf_a, stream);
-                    else
-                        bd::launch_stem4(lm, step, plan.map, (int)w0, gw, e->conv1_w, e->conv1_b, sep[0], sep[1], buf_a, stream);
-                };
-                stem_launch();
-                BD_REPEAT_EXTRA(5) stem_launch();
-            }
-            last = buf_a;
-            last_floats = (int64_t)gw * 24 * 16 * 128;
-            stopped = stop_stage == 4;
-            first_layer = 2;
-        } else if (mode == 0 && e->fuse_stem && !calibrating && stop_stage < 0) {
-            // exact-f32 mode: layers 1-3 as one kernel on v_mfma_f32_32x32x2_f32 (sepf32.hip), bit-identical to the five
-            // kernels it replaces (the calibration pass and the stage taps keep one kernel per op)
-            {
-                Scope sc(e, stream, 5);
-                // (the layer-2 tile handed over in registers, stemregf32.hip; the form of rounds 4-5 with its tiles through LDS
-                //  - stem3_f32_kernel / l4_f32_kernel, sepf32.hip - was removed in round 6: stem = 5 runs this one too)
-                auto stem_launch = [&]() {
-                    bd::launch_stem_reg_f32(lm, step, plan.map, (int)w0, gw, e->conv1_w, e->conv1_b, sep[0], sep[1], buf_a, stream);
-                };
-                stem_launch();
-                BD_REPEAT_EXTRA(5) stem_launch();
-            }
-            last = buf_a;
-            last_floats = (int64_t)gw * 24 * 16 * 128;
-            first_layer = 2;
-            f32_l4 = e->fuse_sep;
-        } else {
-            {
-                Scope sc(e, stream, 1);
-                bd::launch_conv1(lm, step, plan.map, (int)w0, gw, e->conv1_w, e->conv1_b, buf_a, stream);
-            }
-            last = buf_a;
-            last_floats = (int64_t)gw * 48 * 32 * 32;
-            stopped = stop_stage == 0;
-        }
-        bool pooled_done = false;    // the last layer's kernel already produced the pooled embeddings
-        for (int l = first_layer; l < 13 && !stopped; ++l) {
-            const bd::SepLayer& L = sep[l];
-            // pointwise 5 -> layer 6 -> depthwise 7 -> pointwise 7 as ONE launch, a window per tile, tiles on the CU (sepmid.hip):
-            // reads the depthwise-5 output the layer-4 kernel left in buf_b, writes the layer-7 output into buf_a; timed in
-            // layer 7's pointwise slot
-            if (l == 3 && skip_dw_layer == 3 && e->fuse_sep && e->chip_mid && mode != 0 && stop_stage < 0 &&
-                bd::launch_separable_mid(buf_b, buf_a, gw, sep[3], sep[4], sep[5], stream)) {
-                BD_REPEAT_EXTRA(13) (void)bd::launch_separable_mid(buf_b, buf_a, gw, sep[3], sep[4], sep[5], stream);
-                l = 5;
-                if (e->profiling) Scope::mark(e, stream, 3 + 2 * l);
-                last = buf_a;
-                last_floats = (int64_t)gw * sep[5].h_out * sep[5].w_out * sep[5].cout;
-                continue;
-            }
-            // layers 8-12 + the stride-2 depthwise of layer 13 as ONE launch whose tiles stay on the CU (sepchip.hip): reads
-            // buf_a, writes only [windows][3][2][512] into buf_b; timed in layer 12's pointwise slot
-            if (e->fuse_sep && mode != 0 && stop_stage < 0 && skip_dw_layer != l) {
-                // ... and with the tail behind it on septail.hip's kernel, that output leaves as f16 hi / lo planes
-                const bool planes = l == 6 && gw <= (1 << 18) && bd::tail_supported(sep[11], sep[12]);   // (2^18 windows: the tail kernel's 32-bit offsets)
-                const int ran = bd::launch_separable_run_next_dw(buf_a, buf_b, gw, &sep[l], 13 - l, stream, planes);
-                if (ran > 0) {
-                    BD_REPEAT_EXTRA(3 + 2 * (l + ran - 1)) (void)bd::launch_separable_run_next_dw(buf_a, buf_b, gw, &sep[l], 13 - l, stream, planes);
-                    l += ran - 1;
-                    if (e->profiling) Scope::mark(e, stream, 3 + 2 * l);
-                    if (planes) {
-                        // pointwise 13 + depthwise 14 (planes buf_b -> planes buf_a), pointwise 14 + average pool (-> [windows][1024]),
-                        // timed in the two layers' pointwise slots
-                        float* pooled = emb ? emb + w0 * BD_EMBEDDING_SIZE : buf_b;
-                        (void)bd::launch_tail_pw13_dw14(buf_b, buf_a, gw, sep[11], sep[12], stream);
-                        BD_REPEAT_EXTRA(25) (void)bd::launch_tail_pw13_dw14(buf_b, buf_a, gw, sep[11], sep[12], stream);
-                        if (e->profiling) Scope::mark(e, stream, 25);
-                        (void)bd::launch_tail_pw14_pool(buf_a, pooled, gw, sep[12], stream);
-                        BD_REPEAT_EXTRA(27) (void)bd::launch_tail_pw14_pool(buf_a, pooled, gw, sep[12], stream);
-                        if (e->profiling) Scope::mark(e, stream, 27);
-                        if (logits) {
-                            Scope sc(e, stream, 28);
-                            bd::launch_head(pooled, gw, e->head_wt, e->head_b, e->n_classes, logits + w0 * e->n_classes, stream);
-                            BD_REPEAT_EXTRA(28)
-                                bd::launch_head(pooled, gw, e->head_wt, e->head_b, e->n_classes, logits + w0 * e->n_classes, stream);
-                        }
-                        pooled_done = true;
-                        break;
-                    }
-                    skip_dw_layer = l + 1;
-                    last = buf_b;
-                    last_floats = (int64_t)gw * sep[l + 1].h_out * sep[l + 1].w_out * sep[l].cout;
-                    continue;
-                }
-            }
-            // stride-1 layers: depthwise inside the GEMM (split-f16 mode), unless a test taps the depthwise
-            // ... and when the NEXT layer is a stride-2 one, its depthwise is applied in that kernel's epilogue
-            // (whole-window tiles): the kernel then writes the next layer's depthwise output into buf_b
-            if (e->fuse_sep && mode != 0 && l + 1 < 13 && (stop_stage < 0 || stop_stage >= 2 * (l + 1) + 2) &&
-                bd::launch_separable_fused_next_dw(buf_a, buf_b, gw, L, sep[l + 1], stream)) {
-                BD_REPEAT_EXTRA(3 + 2 * l) (void)bd::launch_separable_fused_next_dw(buf_a, buf_b, gw, L, sep[l + 1], stream);
-                if (e->profiling) Scope::mark(e, stream, 3 + 2 * l);
-                skip_dw_layer = l + 1;
-                last = buf_b;
-                last_floats = (int64_t)gw * sep[l + 1].h_out * sep[l + 1].w_out * L.cout;
-                continue;
-            }
-            // exact-f32 mode: pointwise 5 + layer 6 + layer 7 as ONE launch (sepmidf32.hip): depthwise 5 has been applied by
-            // l4_f32_kernel (buf_b); the layer-7 output lands in buf_a like any pointwise output
-            if (f32_l4 && l == 3 && skip_dw_layer == 3 && e->chip_mid && stop_stage < 0 &&
-                bd::launch_separable_mid_f32(buf_b, buf_a, gw, sep[3], sep[4], sep[5], stream)) {
-                BD_REPEAT_EXTRA(13) (void)bd::launch_separable_mid_f32(buf_b, buf_a, gw, sep[3], sep[4], sep[5], stream);
-                l = 5;
-                if (e->profiling) Scope::mark(e, stream, 3 + 2 * l);
-                last = buf_a;
-                last_floats = (int64_t)gw * 6 * 4 * 512;
-                continue;
-            }
-            // exact-f32 mode: layers 8-12 + the depthwise of layer 13 as ONE launch whose tiles stay on the CU (sepchipf32.hip).
-            // Its input is the layer-7 output (buf_a) or, when the launch in front applied depthwise 8 in its epilogue, that
-            // (buf_b); layer 13 then starts at its 1x1 convolution on the depthwise-13 output in buf_b
-            if (f32_l4 && l == 6 && stop_stage < 0) {
-                const bool dw8_done = skip_dw_layer == 6;
-                float* const src = dw8_done ? buf_b : buf_a;
-                float* const dst = dw8_done ? buf_a : buf_b;
-                if (bd::launch_separable_chip_f32(src, dst, gw, &sep[6], 5, stream, &sep[11], dw8_done)) {
-                    BD_REPEAT_EXTRA(23) (void)bd::launch_separable_chip_f32(src, dst, gw, &sep[6], 5, stream, &sep[11], dw8_done);
-                    l = 10;
-                    if (e->profiling) Scope::mark(e, stream, 3 + 2 * l);
-                    if (dw8_done) {
-                        float* t = buf_a;
-                        buf_a = buf_b;
-                        buf_b = t;
-                    }
-                    skip_dw_layer = 11;
-                    last = buf_b;
-                    last_floats = (int64_t)gw * 3 * 2 * 512;
-                    continue;
-                }
-            }
-            // exact-f32 mode: pointwise 13 + depthwise 14 and pointwise 14 + pool on septail.hip's kernel (depthwise 13 has been applied
-            // by the on-chip run: buf_b -> buf_a -> [windows][1024]), timed in the two layers' pointwise slots
-            if (f32_l4 && l == 11 && skip_dw_layer == 11 && stop_stage < 0 && gw <= (1 << 17) && bd::tail_f32_supported(sep[11], sep[12])) {
-                float* pooled = emb ? emb + w0 * BD_EMBEDDING_SIZE : buf_b;
-                (void)bd::launch_tail_f32(buf_b, buf_a, pooled, gw, sep[11], sep[12], stream, 0);
-                BD_REPEAT_EXTRA(25) (void)bd::launch_tail_f32(buf_b, buf_a, pooled, gw, sep[11], sep[12], stream, 0);
-                if (e->profiling) Scope::mark(e, stream, 25);
-                (void)bd::launch_tail_f32(buf_b, buf_a, pooled, gw, sep[11], sep[12], stream, 1);
-                BD_REPEAT_EXTRA(27) (void)bd::launch_tail_f32(buf_b, buf_a, pooled, gw, sep[11], sep[12], stream, 1);
-                if (e->profiling) Scope::mark(e, stream, 27);
-                if (logits) {
-                    Scope sc(e, stream, 28);
-                    bd::launch_head(pooled, gw, e->head_wt, e->head_b, e->n_classes, logits + w0 * e->n_classes, stream);
-                    BD_REPEAT_EXTRA(28)
-                        bd::launch_head(pooled, gw, e->head_wt, e->head_b, e->n_classes, logits + w0 * e->n_classes, stream);
-                }
-                pooled_done = true;
-                break;
-            }
-            // exact-f32 mode, behind the f32 stem: layer 4 and layer 5's stride-2 depthwise as one kernel (bit-identical to the
-            // three it replaces); layer 5 then starts at its 1x1 convolution
-            // (the layer-4 tile handed to depthwise 5 in registers, l4regf32.hip)
-            auto l4_launch = [&]() { return bd::launch_l4_reg_f32(buf_a, buf_b, gw, L, sep[3], stream); };
-            if (f32_l4 && l == 2 && l4_launch()) {
-                BD_REPEAT_EXTRA(3 + 2 * l) (void)l4_launch();
-                if (e->profiling) Scope::mark(e, stream, 3 + 2 * l);
-                skip_dw_layer = 3;
-                last = buf_b;
-                last_floats = (int64_t)gw * 12 * 8 * 128;
-                continue;
-            }
-            if (skip_dw_layer != l) {
-                Scope sc(e, stream, 2 + 2 * l);
-                bd::launch_depthwise(buf_a, buf_b, gw, L, stream);
-            }
-            last = buf_b;
-            last_floats = (int64_t)gw * L.h_out * L.w_out * L.cin;
-            if (stop_stage == 2 * l + 1) {
-                stopped = true;
-                break;
-            }
-            // exact-f32 mode behind the f32 stem: the 1x1 convolution with the NEXT layer's depthwise in its epilogue (whole
-            // windows per 96-row tile; bit-identical to the two kernels): the 1x1 output never reaches HBM and the next
-            // layer starts at its own 1x1 convolution.  Timed in this layer's pointwise slot.
-            if (f32_l4 && l + 1 < 13 && bd::launch_pointwise_next_dw_f32(buf_b, buf_a, gw, L, sep[l + 1], stream)) {
-                BD_REPEAT_EXTRA(3 + 2 * l) (void)bd::launch_pointwise_next_dw_f32(buf_b, buf_a, gw, L, sep[l + 1], stream);
-                if (e->profiling) Scope::mark(e, stream, 3 + 2 * l);
-                float* t = buf_a;                // the next layer's depthwise output is what buf_b holds from here on
-                buf_a = buf_b;
-                buf_b = t;
-                skip_dw_layer = l + 1;
-                last = buf_b;
-                last_floats = (int64_t)gw * sep[l + 1].h_out * sep[l + 1].w_out * L.cout;
-                continue;
-            }
-            {
-                Scope sc(e, stream, 3 + 2 * l);
-                bd::launch_pointwise(buf_b, buf_a, (int64_t)gw * L.h_out * L.w_out, L, stream);
-                BD_REPEAT_EXTRA(3 + 2 * l) bd::launch_pointwise(buf_b, buf_a, (int64_t)gw * L.h_out * L.w_out, L, stream);
-            }
-            last = buf_a;
-            last_floats = (int64_t)gw * L.h_out * L.w_out * L.cout;
-            if (stop_stage == 2 * l + 2) stopped = true;
-        }
+        });
+    for (int64_t w0 = 0; w0 < n_windows; w0 += group) {
+        const int gw = stop_stage >= 0 ? tap_windows : (int)(n_windows - w0 < group ? n_windows - w0 : group);
+        Group g{e, sep, stream, logmel, &plan.map, step, (int)w0, gw, buf_a, buf_b,
+                emb ? emb + w0 * BD_EMBEDDING_SIZE : nullptr, logits ? logits + w0 * e->n_classes : nullptr};
+        if (stop_stage >= 0 || calibrating || (mode == 0 && e->stem == 0)) rc = pass_per_op(g, stop_stage);
+        else rc = mode != 0 ? pass_f16(g) : pass_f32(g);
+        if (rc < 0) return rc;
         if (stop_stage >= 0) {
-            if (mode != 0 && (stop_stage & 1)) {
+            // the tap: stage 0 is layer 2's input, stage 2 l + 1 / 2 l + 2 the depthwise / 1x1 output of layer index l
+            const bool dw = stop_stage & 1;
+            const bd::SepLayer& L = sep[stop_stage == 0 ? 0 : (stop_stage - 1) / 2];
+            const int64_t floats = stop_stage == 0 ? (int64_t)gw * L.h_in * L.w_in * L.cin
+                                                   : (int64_t)gw * L.h_out * L.w_out * (dw ? L.cin : L.cout);
+            if (mode != 0 && dw) {
                 // a depthwise output of the f16 modes carries its layer's power-of-two activation scale: hand out the true values
-                bd::launch_scale_copy(last, tap_out, last_floats, std::ldexp(1.0f, -sep[(stop_stage - 1) / 2].act_exp), stream);
+                bd::launch_scale_copy(g.b, tap_out, floats, std::ldexp(1.0f, -L.act_exp), stream);
             } else {
-                BD_HIP(hipMemcpyAsync(tap_out, last, last_floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
+                BD_HIP(hipMemcpyAsync(tap_out, dw ? g.b : g.a, floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
             }
             break;
-        }
-        if (!pooled_done) {
-            Scope sc(e, stream, 28);
-            bd::launch_pool_head(buf_a, gw, e->head_wt, e->head_b, e->n_classes,
-                                 emb ? emb + w0 * BD_EMBEDDING_SIZE : nullptr,
-                                 logits ? logits + w0 * e->n_classes : nullptr, stream);
         }
     }
     BD_HIP(hipGetLastError());
@@ -1405,11 +1343,8 @@ int bd_set_fusion(bd_handle h, int32_t stem, int32_t separable) {
     if (stem != 0 && stem != 3 && stem != 5) return fail(BD_EINVAL, "bd_set_fusion: stem must be 0, 3 or 5");
     if (separable != 0 && separable != 1 && separable != 10)
         return fail(BD_EINVAL, "bd_set_fusion: separable must be 0, 1 or 10");
-    h->fuse_stem = stem != 0;
-    h->stem_reg = stem == 3;                 // 3 (default): the layer-2 tile handed over in registers (stemreg.hip); 5: through LDS, a
-                                             //    workgroup per row block (stem3_kernel, the default until round 5)
-    h->fuse_sep = separable != 0;
-    h->chip_mid = separable == 1;            // 10: layers 5-7 on the four kernels of round 4
+    h->stem = stem;
+    h->separable = separable;
     return BD_OK;
 }
 

@@ -297,15 +297,20 @@ BD_API int bd_range_flag_copy(bd_handle h, int32_t* dst, int32_t reset, void* st
                    average pool, two launches of one matrix kernel that gives every SIMD of the chip one 96 x 64 tile
                    (septail.hip).  The exact-f32 mode (bd_set_pointwise_mode 0): layers 1-3 one f32-MFMA
                    kernel, layer 4 + depthwise 5 another, the two on-chip launches with f32 stage tiles (sepmidf32.hip,
-                   sepchipf32.hip), layers 13 / 14 as 1x1 kernels with the next depthwise / the pool in their epilogue;
+                   sepchipf32.hip), pointwise 13 + depthwise 14 and pointwise 14 + average pool as two launches of
+                   septail.hip's exact-f32 kernel (groups of up to 2^17 windows; larger groups run layers 13 / 14 one kernel
+                   per op);
    separable == 10 as 1 with layers 5-7 on the four kernels of round 4 (pointwise 5, layer 6 + depthwise 7, pointwise 7).
    Removed in round 6 (BD_EINVAL): stem 2 (layers 1-2 + depthwise 3 only), stem 4 (the walk of stemroll.hip); separable 2
    (layer 4 as band tiles), 3 (a launch per layer for layers 8-11), 4 / 5 (layer 12 / 14 on the 8-wave kernel), 6 (one
    exact-f32 kernel per separable layer, sepf32.hip), 7 (layers 8-11 as the round-3 run through global memory, layers 12 and
    14 on the 12-wave kernel: deleted with that kernel when layers 13 / 14 moved to septail.hip), 8 (the on-chip run ending at
    layer 11), 9 / 12 (plain fused layers).
-   With stem == 0 or during calibration / stage taps inside a fused group: one kernel per op.  Fused and unfused paths give
-   bit-identical results. */
+   stem == 0 runs layers 1-3 one kernel per op; in the exact-f32 mode it turns off the separable fusions too.  Calibration
+   and the stage taps of the exact-f32 mode run one kernel per op.  A stage tap in a split-f16 mode keeps the fused stem
+   when the tapped stage is 4 or later (stemreg.hip only for stage 4 with stem 3, else stem3_kernel), and a stride-1 layer
+   keeps the next layer's stride-2 depthwise in its epilogue when the tap is at or behind that next layer's 1x1 output;
+   it never runs the on-chip launches or septail.hip.  Fused and unfused paths give bit-identical results. */
 BD_API int bd_set_fusion(bd_handle h, int32_t stem, int32_t separable);
 /* whi/wlo: [n][k] f16 halves of wt * scale[n] (wt[n][:] * scale[n] ~= whi[n][:] + wlo[n][:]); unscale[n] = 1 / (scale[n] *
    the scale the caller applied to a): c = relu(fma(acc, unscale[n], bias[n])) */

@@ -833,8 +833,8 @@ def test_fused_f32_mode_equals_one_kernel_per_op(engine, windows):
     (conv1_kernel, depthwise_kernel, pointwise_kernel): the same chains of IEEE operations, so logits AND embeddings agree
     bit for bit; whole hop and half hop, partial tiles of every layer (windows x positions is not a multiple of the 96 ..
     512-row tiles; windows not a multiple of the 4 / 16 windows of a tile of the depthwise epilogue), two passes (1090).
-    Default: layers 1-3 as stem_reg_f32_kernel, layer 4 + depthwise 5 as l4_reg_f32_kernel, the two on-chip runs, layers 13 / 14
-    as 1x1 kernels with the next depthwise / the pool in their epilogue (pointwise_kernel<96, 128, 1, 4, NH, NW, NS>)."""
+    Default: layers 1-3 as stem_reg_f32_kernel, layer 4 + depthwise 5 as l4_reg_f32_kernel, the two on-chip runs, pointwise 13 +
+    depthwise 14 and pointwise 14 + pool as the two launches of tail_gemm_f32_kernel (septail.hip)."""
     x = O.synthetic_audio(HOP * (windows - 1) + 15600, seed=windows)
     engine.set_pointwise_mode("f32")
     try:
@@ -842,10 +842,10 @@ def test_fused_f32_mode_equals_one_kernel_per_op(engine, windows):
         ref = engine.predict(x, 0.96).numpy()
         ref_emb = engine.embed(x, 0.96).numpy()
         ref_half = engine.predict(x[: HOP * 40], 0.48).numpy()
-        # the default (round 5): layers 1-3 as stem3_f32_kernel, layer 4 + depthwise 5 as l4_f32_kernel, pointwise 5 + layers 6-7
-        # and layers 8-12 + depthwise 13 as the two on-chip runs (sepmidf32.hip, sepchipf32.hip), layers 13 / 14 as 1x1 kernels
-        # with the next depthwise / the pool in their epilogue; 10 = without the middle run (the chip run then takes the
-        # depthwise-8 output)
+        # the default: layers 1-3 as stem_reg_f32_kernel, layer 4 + depthwise 5 as l4_reg_f32_kernel, pointwise 5 + layers 6-7
+        # and layers 8-12 + depthwise 13 as the two on-chip runs (sepmidf32.hip, sepchipf32.hip), layers 13 / 14 on
+        # tail_gemm_f32_kernel (septail.hip); 10 = without the middle run (pointwise 5, 6 and 7 each with the next depthwise in
+        # its epilogue, and the chip run then takes the depthwise-8 output)
         for code in (True, 10):
             engine.set_fusion(True, code)
             assert np.array_equal(engine.predict(x, 0.96).numpy(), ref), code
