@@ -36,6 +36,11 @@ const int kLayerDefs[14][2] = {{2, 32},  {1, 64},  {2, 128}, {1, 128}, {2, 256},
 constexpr int64_t kFloatsA = 98304;   // largest activation per window held in buffer A (layer 2 output 48x32x64)
 constexpr int64_t kFloatsB = 49152;   // largest per window in buffer B (layer-2 depthwise output 48x32x32)
 constexpr int kDefaultGroup = 1024;
+// The largest pass bd_set_group_windows accepts: the size tests/test_pass_size.py runs every launch set at.  Its buffer A
+// is 25.8 GB, so every activation tensor of a pass crosses 2^31 and 2^32 bytes below it.
+constexpr int kMaxGroup = 65536;
+// septail.hip's kernels take 32-bit byte offsets: up to 2^18 windows (split-f16 planes), 2^17 (exact f32)
+static_assert(kMaxGroup <= 1 << 17, "the tail launchers of pass_f16 / pass_f32 cover the largest pass");
 
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
@@ -605,7 +610,7 @@ int bd_destroy(bd_handle h) {
 }
 
 int bd_set_group_windows(bd_handle h, int32_t windows) {
-    if (!h || windows < 0) return fail(BD_EINVAL, "bd_set_group_windows: bad argument");
+    if (!h || windows < 0 || windows > kMaxGroup) return fail(BD_EINVAL, "bd_set_group_windows: windows must be in 0..65536");
     h->group_windows = windows == 0 ? kDefaultGroup : windows;
     return BD_OK;
 }
@@ -940,8 +945,8 @@ int pass_f16(Group& g) {
         pointwise(g, 5);
     }
     // layers 8-12 + depthwise 13 as one on-chip launch (sepchip.hip): a -> b, as the f16 hi / lo planes septail.hip reads
-    // when its kernel can follow (32-bit offsets: up to 2^18 windows), else as f32 for one kernel per op
-    const bool planes = g.gw <= (1 << 18) && bd::tail_supported(sep[11], sep[12]);
+    // when its kernel can follow, else as f32 for one kernel per op
+    const bool planes = bd::tail_supported(sep[11], sep[12]);
     if (!g.launch(23, [&] { return bd::launch_separable_run_next_dw(g.a, g.b, g.gw, &sep[6], 7, g.stream, planes); }))
         return walk_layers(g, 6, false, -1);
     if (!planes) return walk_layers(g, 11, true, -1);
@@ -984,9 +989,8 @@ int pass_f32(Group& g) {
         }))
         return walk_layers(g, 6, dw8_done, -1);
     if (dw8_done) std::swap(g.a, g.b);
-    // pointwise 13 + depthwise 14 (b -> a), pointwise 14 + average pool (-> [windows][1024]) on septail.hip (32-bit byte
-    // offsets: up to 2^17 windows)
-    if (g.gw > (1 << 17) || !bd::tail_f32_supported(sep[11], sep[12])) return walk_layers(g, 11, true, -1);
+    // pointwise 13 + depthwise 14 (b -> a), pointwise 14 + average pool (-> [windows][1024]) on septail.hip
+    if (!bd::tail_f32_supported(sep[11], sep[12])) return walk_layers(g, 11, true, -1);
     float* const pooled = g.emb ? g.emb : g.b;
     if (!g.launch(25, [&] { return bd::launch_tail_f32(g.b, g.a, pooled, g.gw, sep[11], sep[12], g.stream, 0); }) ||
         !g.launch(27, [&] { return bd::launch_tail_f32(g.b, g.a, pooled, g.gw, sep[11], sep[12], g.stream, 1); }))

@@ -70,13 +70,14 @@ __global__ __launch_bounds__(256, 2) void l4_reg_f32_kernel(const float* __restr
     // stored to LDS): l4_f32_kernel on why
     float4 band[4];
     unsigned band_ok = 0;
-    // (global memory through buffer resources: one 32-bit offset register per access instead of a 64-bit address)
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, (unsigned)((size_t)windows * kH * kW * kC * 4), 0x00020000);
+    // (global memory through buffer resources: one 32-bit offset register per access instead of a 64-bit address.  The input
+    // and output resources span one window from a 64-bit base, so no offset exceeds a window's 196 608 / 49 152 bytes at any
+    // pass size; win is uniform, the resources stay in scalar registers)
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W4), 0, kC * kC * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(out, 0, (unsigned)((size_t)windows * 12 * 8 * kC * 4), 0x00020000);
     const unsigned w4off = ((32 * wave + frow) * kC + 4 * fh) * 4;
     auto fetch_band = [&](int win, int r_first, int kc, int rows) {     // input rows r_first - 1 .. r_first + rows - 2
-        const unsigned xin = (unsigned)win * (kH * kW * kC * 4);
+        const __amdgpu_buffer_rsrc_t xrs =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X) + (size_t)win * (kH * kW * kC), 0, kH * kW * kC * 4, 0x00020000);
         band_ok = 0;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void l4_reg_f32_kernel(const float* __restr
             const bool ok = row < rows && ih >= 0 && ih < kH && iw >= 0 && iw < kW;
             band_ok |= ok ? 1u << u : 0u;
             const int ihc = ih < 0 ? 0 : ih >= kH ? kH - 1 : ih, iwc = iw < 0 ? 0 : iw >= kW ? kW - 1 : iw;
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(xrs, xin + (unsigned)(((ihc * kW + iwc) * kC + kc * kKC + cc * 4) * 4), 0, 0);
+            const auto v = __builtin_amdgcn_raw_buffer_load_b128(xrs, (unsigned)(((ihc * kW + iwc) * kC + kc * kKC + cc * 4) * 4), 0, 0);
             band[u] = __builtin_bit_cast(float4, v);
         }
     };
@@ -230,7 +231,8 @@ __global__ __launch_bounds__(256, 2) void l4_reg_f32_kernel(const float* __restr
             // together and the two retire out of order)
 #pragma unroll
             for (int u = 0; u < 4; ++u) asm volatile("" : "+v"(band[u].x), "+v"(band[u].y), "+v"(band[u].z), "+v"(band[u].w));
-            const unsigned dst = (unsigned)((((win * 12 + 2 * ob + fh) * 8) * kC + ch) * 4);
+            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(out + (size_t)win * (12 * 8 * kC), 0, 12 * 8 * kC * 4, 0x00020000);
+            const unsigned dst = (unsigned)((((2 * ob + fh) * 8) * kC + ch) * 4);
 #pragma unroll
             for (int ow = 0; ow < 8; ++ow) {
                 float a = shift;

@@ -275,6 +275,9 @@ class HipEngine:
 
     # ------------------------------------------------------------------ helpers
     def set_group_windows(self, windows: int) -> None:
+        """Windows per pass through the CNN (``bd_set_group_windows``): 1..65536, 0 = the default of 1024.  The workspace
+        grows by 589 824 bytes per window of the pass (38.7 GB at 65536); a larger value raises ``BuzzdetectHipError``
+        (BD_EINVAL)."""
         with self._lock:
             _lib.check(self._lib.bd_set_group_windows(self._handle, int(windows)))
 

@@ -101,7 +101,8 @@ BD_API int bd_create(bd_handle* out, int device, const bd_weights* weights);
 BD_API int bd_destroy(bd_handle h);
 
 /* windows processed per pass through the CNN (activations of one pass stay cache-resident);
-   0 restores the default. */
+   0 restores the default (1024).  At most 65536: a pass needs 589 824 bytes of workspace per window (38.7 GB at the
+   limit), and tests/test_pass_size.py runs every launch set at that size.  Larger values are refused with BD_EINVAL. */
 BD_API int bd_set_group_windows(bd_handle h, int32_t windows);
 
 /* ---- index arithmetic (host only; bit-exact restatement incl. the float32 ceil) ---- */
@@ -298,8 +299,7 @@ BD_API int bd_range_flag_copy(bd_handle h, int32_t* dst, int32_t reset, void* st
                    (septail.hip).  The exact-f32 mode (bd_set_pointwise_mode 0): layers 1-3 one f32-MFMA
                    kernel, layer 4 + depthwise 5 another, the two on-chip launches with f32 stage tiles (sepmidf32.hip,
                    sepchipf32.hip), pointwise 13 + depthwise 14 and pointwise 14 + average pool as two launches of
-                   septail.hip's exact-f32 kernel (groups of up to 2^17 windows; larger groups run layers 13 / 14 one kernel
-                   per op);
+                   septail.hip's exact-f32 kernel;
    separable == 10 as 1 with layers 5-7 on the four kernels of round 4 (pointwise 5, layer 6 + depthwise 7, pointwise 7).
    Removed in round 6 (BD_EINVAL): stem 2 (layers 1-2 + depthwise 3 only), stem 4 (the walk of stemroll.hip); separable 2
    (layer 4 as band tiles), 3 (a launch per layer for layers 8-11), 4 / 5 (layer 12 / 14 on the 8-wave kernel), 6 (one
