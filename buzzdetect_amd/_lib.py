@@ -133,6 +133,34 @@ FLAC_PROTOTYPES = {
                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
+PCM_ABI_VERSION = 1
+PCM_MAX_COEFS = 32
+PCM_LINEAR, PCM_FLOAT, PCM_ULAW, PCM_ALAW, PCM_IMA_ADPCM, PCM_MS_ADPCM = range(6)
+
+
+class bd_pcm_format(C.Structure):
+    _fields_ = [("codec", C.c_int32), ("channels", C.c_int32), ("bits", C.c_int32), ("big_endian", C.c_int32),
+                ("is_signed", C.c_int32), ("block_align", C.c_int32), ("samples_per_block", C.c_int32), ("n_coefs", C.c_int32),
+                ("coefs", C.c_int16 * (2 * PCM_MAX_COEFS))]
+
+
+class bd_pcm_status(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("end_sample", C.c_int64), ("bad_block", C.c_int64), ("reason", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+PCM_STOP_NAMES = {0: "end", 1: "bad_header", 2: "truncated"}
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_pcm.h
+PCM_PROTOTYPES = {
+    "bd_pcm_abi_version": (C.c_int, []),
+    "bd_pcm_decode_host": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(bd_pcm_format), C.c_int64, C.c_int64, C.c_void_p,
+                                     C.POINTER(bd_pcm_status)]),
+    "bd_pcm_workspace_bytes": (C.c_int64, [C.POINTER(bd_pcm_format), C.c_int64, C.c_int64]),
+    "bd_pcm_decode": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(bd_pcm_format), C.c_int64, C.c_int64, C.c_void_p,
+                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -164,7 +192,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         except (RuntimeError, OSError, subprocess.CalledProcessError) as exc:
             raise RuntimeError(f"{path} is older than its sources and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -172,6 +200,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: ABI version {lib.bd_abi_version()} != {ABI_VERSION}; rebuild")
     if lib.bd_flac_abi_version() != FLAC_ABI_VERSION:
         raise RuntimeError(f"{path}: FLAC ABI version {lib.bd_flac_abi_version()} != {FLAC_ABI_VERSION}; rebuild")
+    if lib.bd_pcm_abi_version() != PCM_ABI_VERSION:
+        raise RuntimeError(f"{path}: PCM ABI version {lib.bd_pcm_abi_version()} != {PCM_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

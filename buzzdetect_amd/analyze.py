@@ -12,8 +12,9 @@ surrounds the hot path:
     streamers -> bounded queue -> analyzers -> writer          src/pipeline/coordination.py:26-194  (buzzdetect_amd/pipeline.py)
 
 One process per GPU walks its share of the recordings (round-robin, ``sharding.shard_indices``).  Inputs are ``.wav``
-(uncompressed) and ``.flac``, whose frames are decoded on the device (flacio.py, csrc/flac.hip); the formats the
-reference reads through PyAV on the CPU (MP3, MP4, ...) are out of scope.
+(uncompressed, or G.711 / ADPCM coded), ``.flac``, ``.aiff``, ``.au``, ``.w64`` and ``.rf64``; FLAC frames and the coded and
+non-WAV sample layouts are decoded on the device (flacio.py / csrc/flac.hip, pcmio.py / csrc/pcmcodec.hip).  The perceptual
+codecs the reference reads through libsndfile / PyAV on the CPU (MP3, Ogg, MP4, ...) are out of scope.
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ from .pipeline import log as _log
 from .wavio import WavTrack  # noqa: F401  (re-exported: the streamer's reader)
 
 AnalyzeReport = Report
-EXTENSIONS = (".wav", ".flac")
+EXTENSIONS = (".wav", ".flac", ".aiff", ".au", ".w64", ".rf64")   # libsndfile's format names, as the reference matches them
 STREAMERS_PER_ANALYZER = 3        # the reference runs 8 decoding streamers per GPU analyzer (coordination.py:129-138);
                                   # reading uncompressed PCM (~8 GB/s per thread) needs fewer
 
@@ -56,7 +57,7 @@ def analyze(modelname: str = "model_general_v3", classes_out="all", precision: O
             gather_logits: bool = False, analyzers_cpu: int = 0, stream_buffer_depth: Optional[int] = None,
             verbosity_print: Optional[str] = None, verbosity_log: Optional[str] = None, log_progress: bool = False,
             event_stopanalysis=None) -> AnalyzeReport:
-    """Analyse every ``.wav`` and ``.flac`` under ``dir_audio``; write ``<ident>_buzzdetect.csv`` under ``dir_out``.
+    """Analyse every recording with one of ``EXTENSIONS`` under ``dir_audio``; write ``<ident>_buzzdetect.csv`` under ``dir_out``.
 
     ``classes_out`` / ``precision`` choose activations vs detections exactly as in the reference;
     ``rank`` / ``world_size`` default to the torch.distributed environment (one process per GPU);

@@ -26,11 +26,15 @@ class FlacFormatError(WavFormatError):
 
 
 def open_track(path: str):
-    """WavTrack or FlacTrack, chosen by the file's magic bytes (RIFF / fLaC, an ID3v2 tag before fLaC)."""
+    """WavTrack, FlacTrack or pcmio.PcmTrack, chosen by the file's magic bytes: fLaC (an ID3v2 tag before it allowed),
+    FORM / .snd / the Wave64 riff GUID, RIFF / RF64 with a codec format tag (pcmio.CODEC_TAGS); any other RIFF is WavTrack's."""
+    from . import pcmio
     with open(path, "rb") as f:
-        head = f.read(4)
+        head = f.read(16)
     if head[:4] == b"fLaC" or head[:3] == b"ID3":
         return FlacTrack(path)
+    if pcmio.claims(path, head):
+        return pcmio.PcmTrack(path)
     return WavTrack(path)
 
 

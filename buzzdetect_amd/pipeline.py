@@ -44,6 +44,7 @@ import numpy as np
 
 from . import framing, results
 from .flacio import FlacDecoder, FlacTrack, open_track
+from .pcmio import PcmDecoder, PcmTrack
 from .wavio import WavFormatError, WavTrack
 
 PROGRESS = logging.INFO - 5
@@ -124,7 +125,7 @@ class Report:
     messages: List[str] = field(default_factory=list)
     # wall seconds each stage spent doing its work (summed over the stage's threads; waiting on a queue is not work):
     # read = file -> pinned staging buffer (+ waiting for the copy that still reads it), pin = page-locking the readers'
-    # staging buffers, decode = a FLAC chunk's device decode (enqueue + wait), analyze = enqueueing a batch's kernels, settle = waiting for a batch's range verdict, write_wait = the writer waiting for a batch's event,
+    # staging buffers, decode = a FLAC / pcmio chunk's device decode (enqueue + wait), analyze = enqueueing a batch's kernels, settle = waiting for a batch's range verdict, write_wait = the writer waiting for a batch's event,
     # format = rows -> CSV text, write = appending it to the result files
     busy: Dict[str, float] = field(default_factory=dict)
     end_reason: str = "completed"     # or "interrupted": the caller's stop event ended the run (coordination.py:147-154)
@@ -379,7 +380,7 @@ class Pipeline:
         if os.path.getsize(job.path) < FILE_SIZE_MINIMUM:
             return self._skip("planner", job, f"Skipping {job.shortpath}; below minimum analyzeable size")
         try:
-            track = open_track(job.path)                   # WAV or FLAC, by magic bytes
+            track = open_track(job.path)                   # WAV, FLAC or pcmio's formats, by magic bytes
         except (WavFormatError, OSError) as exc:           # one unreadable recording does not stop the others
             return self._skip("planner", job, f"{exc}; skipping", logging.WARNING,
                               f"unreadable, skipped: {job.shortpath} ({exc})")
@@ -458,6 +459,8 @@ class Pipeline:
             return self._drop(job)
         if isinstance(track, FlacTrack):
             return self._read_flac_unit(unit, a, want, have)
+        if isinstance(track, PcmTrack):
+            return self._read_pcm_unit(unit, a, want, have)
         bpf = track.bytes_per_frame
         out_bpf = bpf if track.is_s16 else track.channels * 4          # any other sample format: float32 on the host
         slot, dev = self.pool.acquire(have * out_bpf, self.aborted)
@@ -561,6 +564,82 @@ class Pipeline:
             got = int(status.samples)
             at = got * track.out_bytes_per_frame
             if got < want:                                 # a frame that fails (or a file cut short) ends the readable audio
+                self._bad_read(job, track, a + got)
+                chunk = (chunk[0], round(chunk[0] + got / track.samplerate, 1))
+            if got == 0:
+                self.pool.release(slot)
+                return self._drop(job)
+            ready = None
+            if st is not None:
+                ready = self.events.take()
+                ready.record(st.stream)
+            with self.lock:
+                self.report.chunks += 1
+                self.report.audio_seconds += float(chunk[1] - chunk[0])
+            self._put(self.q_analyze, ChunkTask(job, chunk, slot, at, got, track.channels, track.samplerate, track.is_s16, ready))
+        except BaseException:
+            self.pool.release(slot)
+            raise
+
+    def _read_pcm_unit(self, unit: ReadUnit, a: int, want: int, have: int) -> None:
+        """An AIFF / AU / Wave64 / coded-WAVE chunk (pcmio.PcmTrack): its bytes as they lie in the file to a device buffer of
+        this reader, decoded there into the pool slot (int16 for 16-bit linear, G.711 and ADPCM, float32 otherwise: what a
+        WAV chunk of the same samples becomes), then the same ChunkTask.  Little-endian 16-bit samples are the slot's
+        bytes already and go straight into it, as a 16-bit WAV chunk does."""
+        from . import _lib
+        import ctypes
+        job, chunk, track = unit.job, unit.chunk, unit.job.track
+        slot, dev = self.pool.acquire(have * track.out_bytes_per_frame, self.aborted)
+        try:
+            t0 = time.perf_counter()
+            bpf = track.out_bytes_per_frame
+            st = None
+            got = 0
+            if self.device is None:                        # host-only stage (tests): the host decoder
+                host = dev.numpy()
+                for p, m in track.pieces(a, have):         # (the same pieces as the device path)
+                    off, end = track.byte_range(p, m)
+                    data = np.frombuffer(os.pread(track.fd, end - off, off), np.uint8)
+                    status = _lib.bd_pcm_status()
+                    _lib.check(_lib.load().bd_pcm_decode_host(data.ctypes.data if data.size else None, data.size,
+                                                              ctypes.byref(track.fmt), p, m, host[(p - a) * bpf:].ctypes.data,
+                                                              ctypes.byref(status)))
+                    got += int(status.samples)
+                    if status.samples < m:
+                        break
+                self._busy("read", time.perf_counter() - t0)
+            else:
+                st = getattr(self._stage, "st", None)
+                if st is None:
+                    st = self._stage.st = ReaderStage.take(self.torch, self.device)
+                    with self.lock:
+                        self._stages.append(st)
+                    self._busy("pin", st.pin_seconds)
+                    t0 = time.perf_counter()
+                if track.raw_s16:
+                    off, end = track.byte_range(a, have)
+                    got = min(st.read(track.fd, off, end - off, dev) // bpf, have)
+                    self._busy("read", time.perf_counter() - t0)
+                else:
+                    dec = getattr(self._stage, "pcm", None)
+                    if dec is None:
+                        dec = self._stage.pcm = PcmDecoder(self.torch, self.device)
+                    for p, m in track.pieces(a, have):     # one piece unless the range reaches PIECE_BYTES
+                        off, end = track.byte_range(p, m)
+                        comp = dec.staging(end - off)
+                        nbytes = st.read(track.fd, off, end - off, comp)
+                        t1 = time.perf_counter()
+                        self._busy("read", t1 - t0)
+                        dec.decode(track, nbytes, p, m, dev.data_ptr() + (p - a) * bpf, st.stream)
+                        st.stream.synchronize()            # (a reader may block; the analyzers never wait for this)
+                        k = int(dec.result().samples)
+                        t0 = time.perf_counter()
+                        self._busy("decode", t0 - t1)
+                        got += k
+                        if k < m:
+                            break
+            at = got * track.out_bytes_per_frame
+            if got < want:                                 # an invalid block header (or a file cut short) ends the audio
                 self._bad_read(job, track, a + got)
                 chunk = (chunk[0], round(chunk[0] + got / track.samplerate, 1))
             if got == 0:
