@@ -167,8 +167,14 @@ int launch_separable_run_next_dw(const float* a, float* b, int windows, const Se
                                  bool planes = false);
 bool launch_separable_fused_next_dw(const float* in, float* out, int windows, const SepLayer& L, const SepLayer& next,
                                     hipStream_t stream);
+// layer 3's 1x1 convolution + layer 4 + depthwise 5 on the planes launch_stem_reg_planes writes (cnn.hip): would it run?
+bool l4_window_planes_supported(const SepLayer& L3, const SepLayer& L4, const SepLayer& L5);
+bool launch_l4_window_planes(const void* planes, const SepLayer& L3, const SepLayer& L4, const SepLayer& L5, float* out,
+                             int windows, hipStream_t stream);
 void launch_stem_reg(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
                      const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);
+void launch_stem_reg_planes(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
+                            const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);   // planes for launch_l4_window_planes
 void launch_stem_reg_f32(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
                          const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);   // stemregf32.hip
 void launch_stem4(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,

@@ -3,12 +3,14 @@
 // All activations are NHWC float32, exactly the reference's layout.
 // TF "SAME" for an even extent with stride 2 pads 0 before / 1 after; stride 1 pads 1 / 1.
 //
-// Default path (7 launches per pass): stem_reg_kernel (stemreg.hip: layers 1-3), l4_window_kernel (here),
+// Default path (7 launches per pass): stem_reg_kernel (stemreg.hip: layers 1-2 + depthwise 3),
+// l4_window_kernel (here: pointwise 3, layer 4, depthwise 5),
 // sep_mid_kernel (sepmid.hip: pointwise 5 + layers 6-7), sep_chip_kernel (sepchip.hip: layers 8-12 + depthwise 13),
 // tail_gemm_kernel twice (septail.hip: pointwise 13 + depthwise 14, pointwise 14 + pool), pool_head_kernel<1>.
 // The kernels of this file:
 //   stem3_kernel         layers 1-3 as one kernel, a workgroup per row block (the default of rounds 2-4; bd_set_fusion stem = 5)
-//   l4_window_kernel     layer 4 + depthwise 5: persistent workgroups walk whole windows two map rows at a time
+//   l4_window_kernel     layer 4 + depthwise 5: persistent workgroups walk whole windows two map rows at a time (PLANES: with
+//                        pointwise 3 in front, on the split-f16 A tiles stem_reg_kernel<.., true> writes)
 //   pw_res_kernel        the 1x1 convolutions of layers 5 and 7: persistent, weights in registers (separable = 10; one kernel per op)
 //   sep_ws_kernel        wave-specialised 96 x 256 tiles (4 producer + 4 MFMA waves, slab ring by LDS-DMA): NDW = 1 = layer 6 +
 //                        depthwise 7 (separable = 10); PWO = a plain 1x1 convolution of a wide layer (one kernel per op)
@@ -1462,13 +1464,20 @@ void launch_pw_res(const float* X, const SepLayer& L, float* out, int M, hipStre
 // tile K - 1, so the pipeline fills once per launch, not once per window; the top and bottom rows of
 // a window take zeros instead of their neighbours' rows.  One barrier per step.  Arithmetic order per element equals
 // depthwise_kernel / pointwise_f16x3_kernel: bit-identical to the unfused path.
-template <bool PLAIN>
+// PLANES (the default launch set since round 7): X is not the layer-3 output but what stem_reg_kernel<.., true> leaves of it
+// before layer 3's 1x1 convolution - its split-f16 A tiles as they lay in the stem's LDS, [window][row pair][hi, lo][2 k-halves]
+// [32 rows][64 B] (8 KB per row pair, half of the f32 rows) - and the matrix waves run that convolution (the stem's phases G and
+// H: the same weight fragments, k order and epilogue, so the same bits) for row pair k + 2 in step k, straight into the ring.
+// Per step they copy the image of row pair k + 3 into one of two 8 KB LDS stages (requested a step earlier, 32 B a lane in
+// place of 64) and run 12 more MFMAs; the ring keeps its lead of two row pairs.
+template <bool PLAIN, bool PLANES>
 __global__ __launch_bounds__(768) void l4_window_kernel(
     const float* __restrict__ X, const float* __restrict__ dw_w, const float* __restrict__ dw_b,
     const _Float16* __restrict__ Wfhi, const _Float16* __restrict__ Wflo, const float* __restrict__ pw_u,
     const float* __restrict__ pw_b,
     const float* __restrict__ ndw_w, const float* __restrict__ ndw_b, float* __restrict__ out, int windows,
-    unsigned* __restrict__ range_flag) {
+    unsigned* __restrict__ range_flag, const _Float16* __restrict__ W3fhi, const _Float16* __restrict__ W3flo,
+    const float* __restrict__ pw3_u, const float* __restrict__ pw3_b) {
     constexpr int H = 24, W = 16, C = 128, K16 = 8, STEPS = H / 2;
     constexpr int COL_B = C * 4;                       // bytes of one map position, f32
     constexpr int ROW_B = (W + 1) * COL_B;             // ring slot of a map row: 16 columns + a zero column
@@ -1481,6 +1490,10 @@ __global__ __launch_bounds__(768) void l4_window_kernel(
                                                        // matrix waves wait for their input rows with a counted vmcnt, which a store
                                                        // of their own in between turns into vmcnt(0) - the vector waves store
     constexpr int O5_ROW = (W / 2) * C * 4, O5_BUF = 2 * O5_ROW;
+    constexpr int PL0 = O5 + 2 * O5_BUF;               // PLANES: two stages of a row pair's split-f16 image [hi, lo][2][32][64 B]
+    constexpr int PL_B = 8192, PL_HALF = 4096;
+    constexpr int W3L = PL0 + 2 * PL_B;                // PLANES, split-f16: layer 3's low weight fragments [wave][4][64 lanes][16 B]
+                                                       // (as registers beside the high ones the matrix waves spill)
     constexpr size_t WIN_IN = (size_t)H * W * C, WIN_OUT = (size_t)STEPS * (W / 2) * C;
     static_assert(A0 % 512 == 0, "fragment addresses are formed by XOR");
     static_assert((2 * STEPS) % 8 == 0 && STEPS % 2 == 0, "ring slots and buffer parities carry over from window to window");
@@ -1521,8 +1534,30 @@ __global__ __launch_bounds__(768) void l4_window_kernel(
 #define BD_L4_STORE(SRC, J)                                                                               \
     _Pragma("unroll") for (int u = 0; u < 4; ++u)                                                         \
         *reinterpret_cast<v4f*>(ring_t + ((2 * (J) + (u >> 1)) & 7) * ROW_B + 8 * (u & 1) * COL_B) = SRC[u];
-        BD_L4_LOAD(rs[0], 0)
-        BD_L4_LOAD(rs[1], 1)
+        // PLANES: the planes of row pair J (as BD_L4_LOAD: J = 12 i + j) - 16 bytes of each plane per thread - and the stage
+        // they go to: stage J & 1
+        const char* const pt = reinterpret_cast<const char*>(X) + (size_t)b * STEPS * PL_B + tid * 16;
+        v4f rp[2], rq[2];                              // the planes of the next row pair for the stages (rq: the prologue's second)
+#define BD_L4_PLOAD(DST, J)                                                                               \
+    {                                                                                                     \
+        const int i_ = (J) / STEPS, j_ = (J) - i_ * STEPS;                                                \
+        const char* const src_ = pt + ((size_t)i_ * G * STEPS + j_) * PL_B;                               \
+        DST[0] = *reinterpret_cast<const v4f*>(src_);                                                     \
+        if constexpr (!PLAIN) DST[1] = *reinterpret_cast<const v4f*>(src_ + PL_HALF);                     \
+    }
+#define BD_L4_PSTORE(SRC, J)                                                                              \
+    {                                                                                                     \
+        char* const st_ = smem + PL0 + ((J) & 1) * PL_B + tid * 16;                                       \
+        *reinterpret_cast<v4f*>(st_) = SRC[0];                                                            \
+        if constexpr (!PLAIN) *reinterpret_cast<v4f*>(st_ + PL_HALF) = SRC[1];                            \
+    }
+        if constexpr (PLANES) {
+            BD_L4_PLOAD(rp, 0)
+            BD_L4_PLOAD(rq, 1)
+        } else {
+            BD_L4_LOAD(rs[0], 0)
+            BD_L4_LOAD(rs[1], 1)
+        }
         f16x8 bh[K16], bl[K16];
 #pragma unroll
         for (int q = 0; q < K16; ++q) {
@@ -1532,20 +1567,85 @@ __global__ __launch_bounds__(768) void l4_window_kernel(
         }
         const int ncol = 32 * wave + frow;
         const float bcol = pw_b[ncol], ucol = pw_u[ncol];
+        // PLANES: layer 3's weight fragments (output channel ncol: the stem's n3) for the whole launch, its scale and shift
+        f16x8 w3h[PLANES ? 4 : 1];
+        char* const w3l = smem + W3L + (wave * 4 * 64 + lane) * 16;      // fragment q at + q * 1024 (each lane reads what it wrote)
+        float u3 = 0.0f, b3 = 0.0f;
+        if constexpr (PLANES) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const size_t frag = ((size_t)(wave * 4 + q) * 64 + lane) * 8;
+                w3h[q] = *reinterpret_cast<const f16x8*>(W3fhi + frag);
+                if constexpr (!PLAIN) *reinterpret_cast<f16x8*>(w3l + q * 1024) = *reinterpret_cast<const f16x8*>(W3flo + frag);
+            }
+            u3 = pw3_u[ncol];
+            b3 = pw3_b[ncol];
+        }
+        // PLANES: layer 3's 1x1 convolution of row pair J from stage J & 1 (stemreg.hip, phases G and H): accumulator element r is
+        // tile row m = 4 fh + (r & 3) + 8 (r >> 2) = map row 2 j + (m >> 4), column m & 15 -> ring slot (2 J + (m >> 4)) & 7
+        // (fragment (row frow, k 16 q + 8 fh ..) of a plane: stemreg.hip's rg_swz64(frow, 2 (q & 1) + fh), i.e. pl_a[q & 1] +
+        //  (q >> 1) * 2048 within the stage; the stage J & 1 is the step's parity, a constant: two address registers, the rest
+        //  immediate offsets - with PL0 > 65535 in the offsets the compiler keeps eight addresses and spills them)
+        typedef const __attribute__((address_space(3))) f16x8* lptrh;
+        unsigned pl_a[2];
+        pl_a[0] = pw_lds_addr(smem) + (unsigned)(PL0 + frow * 64 + ((fh ^ ((frow >> 2) & 3)) << 4));
+        pl_a[1] = pl_a[0] ^ 32u;
+        asm("" : "+v"(pl_a[0]), "+v"(pl_a[1]));
+        auto pw3 = [&](auto stage_c, int J) {
+            constexpr int stage = decltype(stage_c)::value;
+            f32x16 acc3;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc3[r] = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const unsigned a = pl_a[q & 1] + (unsigned)(stage * PL_B + (q >> 1) * 2048);
+                const f16x8 ah = *(lptrh)(size_t)a;
+                if constexpr (!PLAIN) {
+                    const f16x8 al = *(lptrh)(size_t)(a + PL_HALF);
+                    acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, w3h[q], acc3, 0, 0, 0);
+                    acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, *reinterpret_cast<const f16x8*>(w3l + q * 1024), acc3, 0, 0, 0);
+                }
+                acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, w3h[q], acc3, 0, 0, 0);
+            }
+            char* const rw = smem + RING0 + ncol * 4;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = 4 * fh + (r & 3) + 8 * (r >> 2);
+                *reinterpret_cast<float*>(rw + ((2 * J + (m >> 4)) & 7) * ROW_B + (m & 15) * COL_B) = fmaxf(fmaf(acc3[r], u3, b3), 0.0f);
+            }
+        };
         // depthwise 5 of this lane's channel: the four partial sums (output columns 2 fh, 2 fh + 1, 4 + 2 fh, 5 + 2 fh); its taps
         // and shift are read from LDS when a step needs them
         const float* const t5 = reinterpret_cast<const float*>(smem + T5) + ncol * 12;
         float acc5[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         float* const o5 = reinterpret_cast<float*>(smem + O5) + (2 * fh) * C + ncol;
         int s5 = 0;                                    // row tile within its window, of the tile the MFMAs work on
-        BD_L4_STORE(rs[0], 0)
-        BD_L4_STORE(rs[1], 1)
-        BD_L4_LOAD(rs[0], 2)
-        BD_L4_LOAD(rs[1], 3)
+        if constexpr (PLANES) {
+            BD_L4_PSTORE(rp, 0)
+            BD_L4_PSTORE(rq, 1)
+            BD_L4_PLOAD(rp, 2)
+            BD_L4_PLOAD(rq, 3)
+        } else {
+            BD_L4_STORE(rs[0], 0)
+            BD_L4_STORE(rs[1], 1)
+            BD_L4_LOAD(rs[0], 2)
+            BD_L4_LOAD(rs[1], 3)
+        }
 #pragma unroll
         for (int q = 0; q < K16; ++q) {                // the weights are in their registers before the loop (see pw_res_kernel)
             bh[q] = pw_landed(bh[q]);
             if constexpr (!PLAIN) bl[q] = pw_landed(bl[q]);
+        }
+        if constexpr (PLANES) {
+            // row pairs 0 and 1 into the ring, pair 2 into stage 0, pair 3 in registers (three barriers: the vector side waits
+            // at two more than without planes)
+            __syncthreads();
+            pw3(std::integral_constant<int, 0>{}, 0);
+            __syncthreads();
+            BD_L4_PSTORE(rp, 2)
+            rp[0] = rq[0];
+            rp[1] = rq[1];
+            pw3(std::integral_constant<int, 1>{}, 1);
         }
         // fragment (row frow, k 16 q + 8 fh ..) sits in chunk (2 q + fh) ^ (frow & 15) of its row: fr0 ^ (q << 5)
         const unsigned fr0 = pw_lds_addr(smem) + (unsigned)(A0 + frow * 2 * C + ((fh ^ (frow & 15)) << 4));
@@ -1583,9 +1683,17 @@ __global__ __launch_bounds__(768) void l4_window_kernel(
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[q], acc, 0, 0, 0);
                 });
             }
-            // the input rows two steps ahead into the ring, a request for those four steps ahead (under the last MFMAs)
-            if (k + 2 < NT) { BD_L4_STORE(rs[p], k + 2) }
-            if (k + 4 < NT) BD_L4_LOAD(rs[p], k + 4)
+            if constexpr (PLANES) {
+                // the planes of row pair k + 3 into stage p ^ 1 (read in step k - 1), a request for those of pair k + 4 (a step
+                // ahead: two in flight cost the registers of the weights); row pair k + 2 goes into the ring (from stage p,
+                // written in step k - 1) at the end of the step
+                if (k + 3 < NT) BD_L4_PSTORE(rp, k + 3)
+                if (k + 4 < NT) BD_L4_PLOAD(rp, k + 4)
+            } else {
+                // the input rows two steps ahead into the ring, a request for those four steps ahead (under the last MFMAs)
+                if (k + 2 < NT) { BD_L4_STORE(rs[p], k + 2) }
+                if (k + 4 < NT) BD_L4_LOAD(rs[p], k + 4)
+            }
             if (k >= 1 && k <= NT) {
                 // ---- bias + ReLU, then depthwise 5 on the tile's two map rows 2 s5, 2 s5 + 1: y[r][0 .. 7] = this lane's columns
                 // {0-3, 8-11} + 4 fh of row r; nb[r][g] = the column behind group g (column 4 / 12 for half 0: the other half's
@@ -1640,6 +1748,9 @@ __global__ __launch_bounds__(768) void l4_window_kernel(
                 }
 #undef BD_L4_IN
             }
+            if constexpr (PLANES) {
+                if (k + 2 < NT) pw3(pc, k + 2);            // (behind layer 4's epilogue: its accumulators and A fragments are dead)
+            }
             __syncthreads();
         };
         for (int k = 0; k < NT + 2; k += 2) {          // (steps 0 .. NT + 1: NT is even; the last one is idle on both sides)
@@ -1648,6 +1759,8 @@ __global__ __launch_bounds__(768) void l4_window_kernel(
         }
 #undef BD_L4_LOAD
 #undef BD_L4_STORE
+#undef BD_L4_PLOAD
+#undef BD_L4_PSTORE
     } else {
         // ================================================================= vector side
         // wave v = 0..7, half-wave hi: channels 4 c4 .. of ONE map column - the even columns in waves 0-3, the odd ones in waves 4-7
@@ -1673,6 +1786,10 @@ __global__ __launch_bounds__(768) void l4_window_kernel(
         const int o_lane = (v & 3) * 64 + lane;        // float4 index within a row of [8][128] f32
         float* const ot = out + (size_t)b * WIN_OUT + (size_t)o_lane * 4;
         int s5 = 0, i5 = 0;
+        if constexpr (PLANES) {                        // the matrix side's prologue: row pairs 0 and 1 into the ring
+            __syncthreads();
+            __syncthreads();
+        }
         __syncthreads();
         auto step = [&](auto pc, int k) {
             constexpr int p = decltype(pc)::value;     // k & 1
@@ -1737,18 +1854,24 @@ __global__ __launch_bounds__(768) void l4_window_kernel(
     range_report(rmax, range_flag);
 }
 
-template <bool PLAIN = false>
-void launch_l4_window(const float* X, const SepLayer& L, const SepLayer& next, float* out, int windows, hipStream_t stream) {
-    if constexpr (!PLAIN) {
-        if (L.pw_mode == 2) return launch_l4_window<true>(X, L, next, out, windows, stream);
-    }
-    constexpr int lds = 512 + 8 * 17 * 512 + 2 * 2 * 32 * 256 + 128 * 12 * 4 + 2 * 2 * 8 * 128 * 4;
+template <bool PLAIN, bool PLANES>
+void launch_l4_window_form(const float* X, const SepLayer* L3, const SepLayer& L, const SepLayer& next, float* out, int windows,
+                           hipStream_t stream) {
+    constexpr int lds = 512 + 8 * 17 * 512 + 2 * 2 * 32 * 256 + 128 * 12 * 4 + 2 * 2 * 8 * 128 * 4 + (PLANES ? (PLAIN ? 2 : 4) * 8192 : 0);
     static std::once_flag lds_once[kMaxDevices];
-    allow_dynamic_lds(&l4_window_kernel<PLAIN>, lds, lds_once);
+    allow_dynamic_lds(&l4_window_kernel<PLAIN, PLANES>, lds, lds_once);
     const int grid = windows < 256 ? windows : 256;           // one persistent workgroup per CU
-    hipLaunchKernelGGL((l4_window_kernel<PLAIN>), dim3((unsigned)grid), dim3(768), lds, stream, X, dw_w_of(L), dw_b_of(L),
+    hipLaunchKernelGGL((l4_window_kernel<PLAIN, PLANES>), dim3((unsigned)grid), dim3(768), lds, stream, X, dw_w_of(L), dw_b_of(L),
                        static_cast<const _Float16*>(L.pw_fhi), static_cast<const _Float16*>(L.pw_flo), L.pw_u, L.pw_b, dw_w_of(next),
-                       dw_b_of(next), out, windows, L.range_flag);
+                       dw_b_of(next), out, windows, L.range_flag,
+                       PLANES ? static_cast<const _Float16*>(L3->pw_fhi) : nullptr,
+                       PLANES ? static_cast<const _Float16*>(L3->pw_flo) : nullptr, PLANES ? L3->pw_u : nullptr,
+                       PLANES ? L3->pw_b : nullptr);
+}
+
+void launch_l4_window(const float* X, const SepLayer& L, const SepLayer& next, float* out, int windows, hipStream_t stream) {
+    if (L.pw_mode == 2) launch_l4_window_form<true, false>(X, nullptr, L, next, out, windows, stream);
+    else launch_l4_window_form<false, false>(X, nullptr, L, next, out, windows, stream);
 }
 
 // --------------------------------------------------------------------------- fused stem + layer-3 depthwise
@@ -2308,6 +2431,21 @@ void launch_pointwise(const float* in, float* out, int64_t rows, const SepLayer&
                                        stream, L.pw_mode == 2, L.range_flag);
     else
         launch_pointwise_variant(in, L.pw_wt, L.pw_b, out, rows, L.cout, L.cin, L.pw_variant, stream);
+}
+
+bool l4_window_planes_supported(const SepLayer& L3, const SepLayer& L4, const SepLayer& L5) {
+    return (L3.pw_mode == 1 || L3.pw_mode == 2) && L4.pw_mode == L3.pw_mode && L3.stride == 2 && L3.cin == 64 &&
+           L3.cout == 128 && L3.h_out == 24 && L3.w_out == 16 && L3.pw_fhi && L3.pw_flo && L4.stride == 1 && L4.h_out == 24 &&
+           L4.w_out == 16 && L4.cin == 128 && L4.cout == 128 && L5.stride == 2 && L5.cin == 128;
+}
+
+bool launch_l4_window_planes(const void* planes, const SepLayer& L3, const SepLayer& L4, const SepLayer& L5, float* out,
+                             int windows, hipStream_t stream) {
+    if (windows <= 0 || !l4_window_planes_supported(L3, L4, L5)) return false;
+    const float* const X = static_cast<const float*>(planes);
+    if (L4.pw_mode == 2) launch_l4_window_form<true, true>(X, &L3, L4, L5, out, windows, stream);
+    else launch_l4_window_form<false, true>(X, &L3, L4, L5, out, windows, stream);
+    return true;
 }
 
 // Fused depthwise+pointwise of layer L followed by the stride-2 depthwise of the NEXT layer; `out` receives

@@ -924,17 +924,25 @@ int walk_layers(Group& g, int from, bool dw_done, int stop_stage) {
 int pass_f16(Group& g) {
     const bd_engine* e = g.e;
     const bd::SepLayer* sep = g.sep;
-    if (e->stem != 0) {
-        // the layer-2 tile handed to depthwise 3 in registers (stemreg.hip), or through LDS (stem3_kernel, stem 5)
-        stem(g, e->stem == 3 ? bd::launch_stem_reg : bd::launch_stem4);
+    if (e->stem == 3 && e->separable != 0 && bd::l4_window_planes_supported(sep[1], sep[2], sep[3])) {
+        // layers 1-2 + depthwise 3 (stemreg.hip), then pointwise 3 + layer 4 + depthwise 5 (l4_window_kernel): a -> b through
+        // the split-f16 A tiles of pointwise 3.  Decided before the stem runs: nothing else reads those planes
+        stem(g, bd::launch_stem_reg_planes);
+        if (!g.launch(7, [&] { return bd::launch_l4_window_planes(g.a, sep[1], sep[2], sep[3], g.b, g.gw, g.stream); }))
+            return fail(BD_EHIP, "l4_window_kernel declined the planes of the stem");
     } else {
-        conv1(g);
-        walk_layers(g, 0, false, 4);
+        if (e->stem != 0) {
+            // the layer-2 tile handed to depthwise 3 in registers (stemreg.hip), or through LDS (stem3_kernel, stem 5)
+            stem(g, e->stem == 3 ? bd::launch_stem_reg : bd::launch_stem4);
+        } else {
+            conv1(g);
+            walk_layers(g, 0, false, 4);
+        }
+        if (e->separable == 0) return walk_layers(g, 2, false, -1);
+        // layer 4 + depthwise 5, a window per workgroup (l4_window_kernel): a -> b
+        if (!g.launch(7, [&] { return bd::launch_separable_fused_next_dw(g.a, g.b, g.gw, sep[2], sep[3], g.stream); }))
+            return walk_layers(g, 2, false, -1);
     }
-    if (e->separable == 0) return walk_layers(g, 2, false, -1);
-    // layer 4 + depthwise 5, a window per workgroup (l4_window_kernel): a -> b
-    if (!g.launch(7, [&] { return bd::launch_separable_fused_next_dw(g.a, g.b, g.gw, sep[2], sep[3], g.stream); }))
-        return walk_layers(g, 2, false, -1);
     // pointwise 5 -> layer 6 -> depthwise 7 -> pointwise 7 as one on-chip launch (sepmid.hip): b -> a.  Separable 10, or the
     // launcher declined: pointwise 5, layer 6 + depthwise 7 (sep_ws_kernel<1, 0>: a -> b), pointwise 7
     if (!(e->separable == 1 &&

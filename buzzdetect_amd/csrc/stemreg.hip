@@ -79,14 +79,17 @@ constexpr int OFF_C1W = OFF_D2W + 10 * 32 * 4;   // 51968: taps and shift of con
                                                  // only wait for a load behind stores with vmcnt(0) - the stores' whole round trip
 constexpr int kRegLds = OFF_C1W + 10 * 32 * 4;   // 53248
 
-template <bool PLAIN>
+// END_DW3: the kernel ends at depthwise 3 and writes the split-f16 A tile of layer 3 as it lies in LDS (swizzle included) to
+// planes = [window][row pair 0..11][hi, lo][2 k-halves][32 rows][64 B] (8 KB per row pair, hi only when PLAIN), which
+// l4_window_kernel<.., true> takes up with layer 3's 1x1 convolution (phases G, H, the same arithmetic): W3f*, pw3_* unused.
+template <bool PLAIN, bool END_DW3>
 __global__ __launch_bounds__(256, 3) void stem_reg_kernel(const float* __restrict__ logmel, int patch_step, const WindowMap map, int w0,
                                                           const float* __restrict__ c1_w, const float* __restrict__ c1_b,
                                                           const float* __restrict__ dw2_w, const float* __restrict__ dw2_b,
                                                           const _Float16* __restrict__ Whi, const _Float16* __restrict__ Wlo,
                                                           const float* __restrict__ pw_u, const float* __restrict__ pw_b,
                                                           const float* __restrict__ dw3_w, const float* __restrict__ dw3_b,
-                                                          float* __restrict__ out, const _Float16* __restrict__ W3fhi,
+                                                          void* __restrict__ out, const _Float16* __restrict__ W3fhi,
                                                           const _Float16* __restrict__ W3flo, const float* __restrict__ pw3_u,
                                                           const float* __restrict__ pw3_b, unsigned* __restrict__ range_flag, int windows) {
     __shared__ __attribute__((aligned(16))) char smem[kRegLds];
@@ -362,8 +365,10 @@ __global__ __launch_bounds__(256, 3) void stem_reg_kernel(const float* __restric
             for (int k = 0; k < 9; ++k) d3w[k] = pd3w[k * 64 + wc * 32 + frow];
             const float d3b = pd3b[wc * 32 + frow];
             f16x8 w3h[4], w3l[4];
+            if constexpr (!END_DW3) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) w3h[q] = *(gptrh)(pw3h + ((size_t)(wave * 4 + q) * 64 + lane) * 8);
+                for (int q = 0; q < 4; ++q) w3h[q] = *(gptrh)(pw3h + ((size_t)(wave * 4 + q) * 64 + lane) * 8);
+            }
             __syncthreads();                               // halo column written; every wave has read the A tile of layer 2
             band_to_lds(13);                               // ... whose bytes take the next tile's log-mel band
             float hal[3] = {0.0f, 0.0f, 0.0f};             // column 16 g + 16: the zero padding for g = 1
@@ -409,37 +414,52 @@ __global__ __launch_bounds__(256, 3) void stem_reg_kernel(const float* __restric
             // what the tile above takes over: this tile's first row
 #pragma unroll
             for (int k = 0; k < 8; ++k) carry[k] = ev[0][k];
-            // (the low halves of the weight fragments only now: with them in flight across phase F the kernel needs more than
-            //  the 168 registers three workgroups per CU leave a lane)
-            if constexpr (!PLAIN) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) w3l[q] = *(gptrh)(pw3l + ((size_t)(wave * 4 + q) * 64 + lane) * 8);
-            }
-            const int n3 = 32 * wave + frow;
-            const float b3 = pb3[n3], u3 = pu3[n3];
-            __syncthreads();                               // the A tile of layer 3 is complete
-            // ---- G: [32][64] x [64][128], one 32 x 32 tile per wave ----
-            f32x16 acc3;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc3[r] = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int off = (q >> 1) * 32 * 64 + rg_swz64(frow, 2 * (q & 1) + fh);
-                const f16x8 ah = *reinterpret_cast<const f16x8*>(smem + OFF_A3H + off);
-                const f16x8 al = *reinterpret_cast<const f16x8*>(smem + OFF_A3L + off);
+            if constexpr (END_DW3) {
+                __syncthreads();                           // the A tile of layer 3 is complete
+                // ---- its LDS image, swizzle and all, to row pair ob of the window's planes: 16 bytes of each plane per thread.  (A
+                //      16-byte store whose data registers are overwritten two vector instructions later has been seen to store
+                //      the new values - DESIGN.md 10: the store and three wait states behind it are one asm statement)
+                typedef __attribute__((address_space(1))) char* gchar;
+                const gchar dst = (gchar)out + ((size_t)win * 12 + ob) * 8192 + tid * 16;
+                const v4f ph = *reinterpret_cast<const v4f*>(smem + OFF_A3H + tid * 16);
+                asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 2" : : "v"(dst), "v"(ph) : "memory");
                 if constexpr (!PLAIN) {
-                    acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, w3h[q], acc3, 0, 0, 0);
-                    acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, w3l[q], acc3, 0, 0, 0);
+                    const v4f pl = *reinterpret_cast<const v4f*>(smem + OFF_A3L + tid * 16);
+                    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 2" : : "v"(dst + 4096), "v"(pl) : "memory");
                 }
-                acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, w3h[q], acc3, 0, 0, 0);
-            }
-            // ---- H: bias + ReLU, [32][128] block of the layer-3 output (rows are consecutive NHWC positions) ----
-            float* dst3 = out + (((size_t)win * 24 + 2 * ob) * 16) * 128;
+            } else {
+                // (the low halves of the weight fragments only now: with them in flight across phase F the kernel needs more than
+                //  the 168 registers three workgroups per CU leave a lane)
+                if constexpr (!PLAIN) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = 4 * fh + (r & 3) + 8 * (r >> 2);
-                const v2f t2v = __builtin_elementwise_fma(v2f{acc3[r & ~1], acc3[r | 1]}, v2f{u3, u3}, v2f{b3, b3});
-                dst3[(size_t)m * 128 + n3] = fmaxf((r & 1) ? t2v.y : t2v.x, 0.0f);
+                    for (int q = 0; q < 4; ++q) w3l[q] = *(gptrh)(pw3l + ((size_t)(wave * 4 + q) * 64 + lane) * 8);
+                }
+                const int n3 = 32 * wave + frow;
+                const float b3 = pb3[n3], u3 = pu3[n3];
+                __syncthreads();                               // the A tile of layer 3 is complete
+                // ---- G: [32][64] x [64][128], one 32 x 32 tile per wave ----
+                f32x16 acc3;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc3[r] = 0.0f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int off = (q >> 1) * 32 * 64 + rg_swz64(frow, 2 * (q & 1) + fh);
+                    const f16x8 ah = *reinterpret_cast<const f16x8*>(smem + OFF_A3H + off);
+                    const f16x8 al = *reinterpret_cast<const f16x8*>(smem + OFF_A3L + off);
+                    if constexpr (!PLAIN) {
+                        acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, w3h[q], acc3, 0, 0, 0);
+                        acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, w3l[q], acc3, 0, 0, 0);
+                    }
+                    acc3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, w3h[q], acc3, 0, 0, 0);
+                }
+                // ---- H: bias + ReLU, [32][128] block of the layer-3 output (rows are consecutive NHWC positions) ----
+                float* dst3 = static_cast<float*>(out) + (((size_t)win * 24 + 2 * ob) * 16) * 128;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = 4 * fh + (r & 3) + 8 * (r >> 2);
+                    const v2f t2v = __builtin_elementwise_fma(v2f{acc3[r & ~1], acc3[r | 1]}, v2f{u3, u3}, v2f{b3, b3});
+                    dst3[(size_t)m * 128 + n3] = fmaxf((r & 1) ? t2v.y : t2v.x, 0.0f);
+                }
             }
             // (no barrier: the next tile's phase B writes the conv band, which lies below the A tile of layer 3; its phase C - the
             //  layer-2 A tile - and the halo words are one / three barriers away)
@@ -450,21 +470,38 @@ __global__ __launch_bounds__(256, 3) void stem_reg_kernel(const float* __restric
 
 }  // namespace
 
-// Layers 1-3 complete with the layer-2 tile handed over in registers: out = [windows][24][16][128], the layer-3 output.
-void launch_stem_reg(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
-                     const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream) {
+// Layers 1-3 complete with the layer-2 tile handed over in registers: out = [windows][24][16][128], the layer-3 output; or
+// (planes) the stem ends at depthwise 3: out = its split-f16 A tiles, [windows][12][8192 B], for launch_l4_window_planes.
+static void launch_stem_reg_form(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
+                                 const float* c1_b, const SepLayer& L2, const SepLayer& L3, void* out, hipStream_t stream,
+                                 bool planes) {
     if (windows <= 0) return;
     long long grid = 3ll * cu_count();                      // three workgroups per CU, each with a contiguous run of the 12 x windows tiles
     if (grid > 12ll * windows) grid = 12ll * windows;
-#define BD_STEM_REG(PLAIN)                                                                                           \
-    hipLaunchKernelGGL((stem_reg_kernel<PLAIN>), dim3((unsigned)grid), dim3(256), 0, stream, logmel, patch_step, map, w0, c1_w,    \
-                       c1_b, dw_w_of(L2), dw_b_of(L2), static_cast<const _Float16*>(L2.pw_whi),                           \
+#define BD_STEM_REG(PLAIN, END_DW3)                                                                                  \
+    hipLaunchKernelGGL((stem_reg_kernel<PLAIN, END_DW3>), dim3((unsigned)grid), dim3(256), 0, stream, logmel, patch_step, map, w0,   \
+                       c1_w, c1_b, dw_w_of(L2), dw_b_of(L2), static_cast<const _Float16*>(L2.pw_whi),                     \
                        static_cast<const _Float16*>(L2.pw_wlo), L2.pw_u, L2.pw_b, dw_w_of(L3), dw_b_of(L3), out,            \
                        static_cast<const _Float16*>(L3.pw_fhi), static_cast<const _Float16*>(L3.pw_flo), L3.pw_u, L3.pw_b,  \
                        L2.range_flag, windows)
-    if (L2.pw_mode == 2) BD_STEM_REG(true);
-    else BD_STEM_REG(false);
+    if (planes) {
+        if (L2.pw_mode == 2) BD_STEM_REG(true, true);
+        else BD_STEM_REG(false, true);
+    } else {
+        if (L2.pw_mode == 2) BD_STEM_REG(true, false);
+        else BD_STEM_REG(false, false);
+    }
 #undef BD_STEM_REG
+}
+
+void launch_stem_reg(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
+                     const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream) {
+    launch_stem_reg_form(logmel, patch_step, map, w0, windows, c1_w, c1_b, L2, L3, out, stream, false);
+}
+
+void launch_stem_reg_planes(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
+                            const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream) {
+    launch_stem_reg_form(logmel, patch_step, map, w0, windows, c1_w, c1_b, L2, L3, out, stream, true);
 }
 
 }  // namespace bd

@@ -286,10 +286,14 @@ BD_API int bd_range_flag_copy(bd_handle h, int32_t* dst, int32_t reset, void* st
    stem == 3       (default) layers 1-3 as one kernel that reads log-mel patches and writes the [24][16][128] layer-3 output
                    (the 402 MB layer-2 tensor never reaches HBM); profile slot 5.  The kernel hands the layer-2 tile to layer 3's
                    depthwise in REGISTERS and carries the rows two tiles share (stemreg.hip; in the exact-f32 mode the same
-                   scheme on v_mfma_f32_32x32x2_f32, stemregf32.hip);
+                   scheme on v_mfma_f32_32x32x2_f32, stemregf32.hip).  In the split-f16 modes with separable != 0 (since
+                   round 7) that kernel stops at layer 3's depthwise and writes the split-f16 A operand of layer 3's 1x1
+                   convolution (96 KB per window instead of 196), and the layer-4 launch opens with that convolution;
+                   stage taps and calibration keep the kernel that writes the layer-3 output;
    stem == 5       as 3 on the kernel of rounds 2-4 (a workgroup per row block, the layer-2 tile through LDS: stem3_kernel;
                    split-f16 modes only - the exact-f32 mode has the one form);
-   separable == 1  (default) layer 4 + depthwise 5 a window per workgroup (l4_window_kernel); pointwise 5, layer 6, depthwise 7
+   separable == 1  (default) layer 4 + depthwise 5 a window per workgroup (l4_window_kernel; behind stem 3 in the split-f16
+                   modes with pointwise 3 in front); pointwise 5, layer 6, depthwise 7
                    and pointwise 7 one on-chip launch, a window per tile (sepmid.hip; timed in layer 7's pointwise slot);
                    layers 8-12 + the stride-2 depthwise of layer 13 ONE launch in which every workgroup takes its four windows
                    through the five layers with the tiles between the layers kept on the CU - accumulators -> depthwise in
