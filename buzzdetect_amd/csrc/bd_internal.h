@@ -163,6 +163,16 @@ bool launch_separable_mid_f32(const float* in, float* out, int windows, const Se
                               hipStream_t stream);   // sepchip.hip
 bool launch_separable_mid(const float* in, float* out, int windows, const SepLayer& L5, const SepLayer& L6, const SepLayer& L7,
                           hipStream_t stream);       // sepmid.hip
+// The split-f16 depthwise-7 output handed from sep_mid_kernel to sep_chip_kernel, per window: [stage 0..7][hi, lo][24 rows
+// (4 oy + ox)][32 channels] f16 (the lo planes are not written in the plain-f16 mode)
+constexpr int kDw7PlaneBytes = 8 * 2 * 24 * 32 * 2;
+bool separable_mid_planes_supported(const SepLayer& L5, const SepLayer& L6, const SepLayer& L7);
+bool launch_separable_mid_planes(const float* in, void* out, int windows, const SepLayer& L5, const SepLayer& L6, const SepLayer& L7,
+                                 hipStream_t stream);
+// pointwise 7 on those planes + layers 8-12 + depthwise 13 (sepchip.hip), out = the planes septail.hip reads
+bool separable_chip_pw7_supported(const SepLayer& L7, const SepLayer* L, int nl, const SepLayer& next, int windows);
+bool launch_separable_chip_pw7(const void* in, float* out, int windows, const SepLayer& L7, const SepLayer* L, int nl,
+                               const SepLayer& next, hipStream_t stream);
 int launch_separable_run_next_dw(const float* a, float* b, int windows, const SepLayer* L, int max_layers, hipStream_t stream,
                                  bool planes = false);
 bool launch_separable_fused_next_dw(const float* in, float* out, int windows, const SepLayer& L, const SepLayer& next,

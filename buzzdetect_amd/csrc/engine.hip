@@ -41,6 +41,7 @@ constexpr int kDefaultGroup = 1024;
 constexpr int kMaxGroup = 65536;
 // septail.hip's kernels take 32-bit byte offsets: up to 2^18 windows (split-f16 planes), 2^17 (exact f32)
 static_assert(kMaxGroup <= 1 << 17, "the tail launchers of pass_f16 / pass_f32 cover the largest pass");
+static_assert(bd::kDw7PlaneBytes <= kFloatsA * 4, "the depthwise-7 planes of the middle run fit buffer a");
 
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
@@ -943,21 +944,32 @@ int pass_f16(Group& g) {
         if (!g.launch(7, [&] { return bd::launch_separable_fused_next_dw(g.a, g.b, g.gw, sep[2], sep[3], g.stream); }))
             return walk_layers(g, 2, false, -1);
     }
-    // pointwise 5 -> layer 6 -> depthwise 7 -> pointwise 7 as one on-chip launch (sepmid.hip): b -> a.  Separable 10, or the
-    // launcher declined: pointwise 5, layer 6 + depthwise 7 (sep_ws_kernel<1, 0>: a -> b), pointwise 7
-    if (!(e->separable == 1 &&
-          g.launch(13, [&] { return bd::launch_separable_mid(g.b, g.a, g.gw, sep[3], sep[4], sep[5], g.stream); }))) {
-        pointwise(g, 3);
-        if (!g.launch(11, [&] { return bd::launch_separable_fused_next_dw(g.a, g.b, g.gw, sep[4], sep[5], g.stream); }))
-            return walk_layers(g, 4, false, -1);
-        pointwise(g, 5);
-    }
-    // layers 8-12 + depthwise 13 as one on-chip launch (sepchip.hip): a -> b, as the f16 hi / lo planes septail.hip reads
-    // when its kernel can follow, else as f32 for one kernel per op
     const bool planes = bd::tail_supported(sep[11], sep[12]);
-    if (!g.launch(23, [&] { return bd::launch_separable_run_next_dw(g.a, g.b, g.gw, &sep[6], 7, g.stream, planes); }))
-        return walk_layers(g, 6, false, -1);
-    if (!planes) return walk_layers(g, 11, true, -1);
+    if (e->separable == 1 && planes && bd::separable_mid_planes_supported(sep[3], sep[4], sep[5]) &&
+        bd::separable_chip_pw7_supported(sep[5], &sep[6], 5, sep[11], g.gw)) {
+        // pointwise 5 -> layer 6 -> depthwise 7 (sepmid.hip), then pointwise 7 -> layers 8-12 -> depthwise 13 (sepchip.hip): b -> a
+        // -> b through the split-f16 depthwise-7 planes, the second launch's output the planes septail.hip reads.  Decided
+        // before the middle run: nothing else reads those planes
+        if (!g.launch(13, [&] { return bd::launch_separable_mid_planes(g.b, g.a, g.gw, sep[3], sep[4], sep[5], g.stream); }))
+            return fail(BD_EHIP, "sep_mid_kernel declined the depthwise-7 planes");
+        if (!g.launch(23, [&] { return bd::launch_separable_chip_pw7(g.a, g.b, g.gw, sep[5], &sep[6], 5, sep[11], g.stream); }))
+            return fail(BD_EHIP, "sep_chip_kernel declined the planes of the middle run");
+    } else {
+        // pointwise 5 -> layer 6 -> depthwise 7 -> pointwise 7 as one on-chip launch (sepmid.hip): b -> a.  Separable 10, or the
+        // launcher declined: pointwise 5, layer 6 + depthwise 7 (sep_ws_kernel<1, 0>: a -> b), pointwise 7
+        if (!(e->separable == 1 &&
+              g.launch(13, [&] { return bd::launch_separable_mid(g.b, g.a, g.gw, sep[3], sep[4], sep[5], g.stream); }))) {
+            pointwise(g, 3);
+            if (!g.launch(11, [&] { return bd::launch_separable_fused_next_dw(g.a, g.b, g.gw, sep[4], sep[5], g.stream); }))
+                return walk_layers(g, 4, false, -1);
+            pointwise(g, 5);
+        }
+        // layers 8-12 + depthwise 13 as one on-chip launch (sepchip.hip): a -> b, as the f16 hi / lo planes septail.hip reads
+        // when its kernel can follow, else as f32 for one kernel per op
+        if (!g.launch(23, [&] { return bd::launch_separable_run_next_dw(g.a, g.b, g.gw, &sep[6], 7, g.stream, planes); }))
+            return walk_layers(g, 6, false, -1);
+        if (!planes) return walk_layers(g, 11, true, -1);
+    }
     // pointwise 13 + depthwise 14 (planes b -> planes a), pointwise 14 + average pool (-> [windows][1024]) on septail.hip
     float* const pooled = g.emb ? g.emb : g.b;
     if (!g.launch(25, [&] { return bd::launch_tail_pw13_dw14(g.b, g.a, g.gw, sep[11], sep[12], g.stream); }) ||

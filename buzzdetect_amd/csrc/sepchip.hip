@@ -58,6 +58,8 @@ struct ChipChain {
     const float* pw_u[kChipMaxLayers];          // [512] epilogue factors
     const float* pw_b[kChipMaxLayers];          // [512]
     const float* ndw_w;                         // NDW: taps [9][512] + shift [512] of the stride-2 depthwise behind the run
+    const _Float16 *w7hi, *w7lo;                // PW7: pointwise 7's weights, B-fragment order [512/32][256/16][64][8]
+    const float *u7, *b7;                       // PW7: its epilogue factors / shifts [512]
 };
 // Pointer `field` of layer `li`, read from the kernel-argument segment with a scalar load (the chain is the kernel's FIRST
 // argument, i.e. at offset 0).  Indexing the by-value argument with a run-time layer makes a scratch copy of it; selecting
@@ -68,7 +70,7 @@ __device__ __forceinline__ const T* chain_ptr(int field, int li) {
     const kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
     return reinterpret_cast<const T*>(ka[field * kChipMaxLayers + li]);
 }
-static_assert(sizeof(ChipChain) == (6 * kChipMaxLayers + 1) * 8, "six tables of five pointers + one");
+static_assert(sizeof(ChipChain) == (6 * kChipMaxLayers + 5) * 8, "six tables of five pointers + five");
 
 // NDW (layer 12 closes the run and layer 13 is a stride-2 layer): the run's output is not written; layer 13's depthwise
 // (3 x 3, stride 2, SAME = pad 0 before / 1 after on the 6 x 4 map: outputs 3 x 2) is applied to it in registers - after the
@@ -76,7 +78,14 @@ static_assert(sizeof(ChipChain) == (6 * kChipMaxLayers + 1) * 8, "six tables of 
 // to Y: the arithmetic of depthwise_kernel (shift, then the taps in row-major order with fmaf, ReLU).
 // PLANES (with NDW): the depthwise-13 output leaves as the two f16 halves the tail's matrix kernel reads (septail.hip): hi plane
 // [windows * 6][512] at Y, lo plane behind it - the split and the range guard of the kernel that would otherwise read it as f32.
-template <bool PLAIN, int NSLOT, bool TRACE = false, bool NDW = false, bool PLANES = false>
+// PW7: the run opens with pointwise 7 (256 -> 512) instead of reading its output: X is then the split-f16 depthwise-7 output
+// sep_mid_kernel<.., DW7OUT> writes (kDw7PlaneBytes per window).  The eight stages of that A operand come in by LDS-DMA
+// (buffer_load_dwordx4 ... lds): a DMA lane reads any address, so the ring's swizzle, the 64-byte skew of rows 48.. and the
+// tile's row order are all chosen on the address side, with no registers in between.  Pointwise 7 then is one more layer of
+// the run with K = 256 (8 stages: no pending ones), its epilogue and the step to depthwise 8 those of every other layer, and
+// its arithmetic is that of the layer-7 loop it replaces (sepmid.hip): lo*hi, hi*lo, hi*hi per k16 step in ascending order,
+// relu(fma(acc, u, b)).
+template <bool PLAIN, int NSLOT, bool TRACE = false, bool NDW = false, bool PLANES = false, bool PW7 = false>
 __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, const float* X, float* Y, int nl,
                                                            long long M, unsigned* __restrict__ range_flag,
                                                            unsigned long long* __restrict__ dbg = nullptr, int tune = 0) {
@@ -165,52 +174,27 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
     // taps [9][512] and shift [512] of a layer are one [10][512] table (engine.hip lays dw_b16 behind dw_w16; the launcher checks)
 #define CHIP_TAPS_RSRC(DW_W) __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DW_W), 0, 10 * K * 4, 0x00020000)
 
-    // ---------------------------------------------------------------------- layer 0: its depthwise reads the run's input
-    // through a buffer resource that covers exactly this tile's valid rows: a row past the end of the batch (tail tile)
-    // reads as zero, with no clamping code, and every load is resource + one per-lane offset register + a scalar row offset
-    const long long rows_left = M - m0;
-    const unsigned tile_bytes = (unsigned)(rows_left < 96 ? rows_left : 96) * (K * 4);
-    {
-        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X) + (size_t)m0 * K, 0, tile_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t taps0 = CHIP_TAPS_RSRC(ch.dw_w[0]);
-        const unsigned xo = (48u * fh * K) * 4 + c4;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int st = j ? wc + 8 : wc;
-            v2f in2[6][4];
-#pragma unroll
-            for (int y = 0; y < 6; ++y)
-#pragma unroll
-                for (int x = 0; x < 4; ++x) {
-                    in2[y][x].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, xo, ((4 * y + x) * K + 32 * st) * 4, 0));
-                    in2[y][x].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, xo, ((24 + 4 * y + x) * K + 32 * st) * 4, 0));
-                }
-            if (j == 0) CHIP_DW(0, st, taps0)
-            else CHIP_DW(1, st, taps0)
-            CHIP_TS()
-            __builtin_amdgcn_sched_barrier(0);    // (the second block's 48 loads hoisted over the first's sums cost a spill)
-        }
-        CHIP_PUBLISH()
-    }
-
-    for (int li = 0; li < nl; ++li) {
-        const _Float16* const Wfhi = chain_ptr<_Float16>(2, li);
-        const _Float16* const Wflo = chain_ptr<_Float16>(3, li);
+    // ---------------------------------------------------------------------- the K loop of one layer (KQ_C: k16 steps), the
+    // weights WHI / WLO in B-fragment order; leaves the layer's product in acc
+    auto k_loop = [&](auto kq_c, const _Float16* const Wfhi, const _Float16* const Wflo) __attribute__((always_inline)) {
+        constexpr int KQL = decltype(kq_c)::value;
+        constexpr int NS = KQL / 2;               // stages
+        constexpr int NP = NS > NSLOT ? NS - NSLOT : 0;    // of which pending
+        static_assert(NP == 0 || NP == NPEND, "a layer of K = 512 or one that fits the ring");
         // B fragments: column tile (wc, wc + 8), k16 step q -> ((tile * KQ + q) * 64 + lane) * 16 bytes: resource + lane * 16 in
         // one register + a scalar offset.  The first k16 step's are requested in FRONT of the barrier that publishes the A
         // operand (round 6): behind it all eight waves would wait out the same L2 round trip at once
-        const __amdgpu_buffer_rsrc_t bhr = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(Wfhi), 0, K * K * 2, 0x00020000);
-        const __amdgpu_buffer_rsrc_t blr = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(Wflo), 0, K * K * 2, 0x00020000);
-        const int btile = wc * (KQ * 1024);       // bytes of a column tile's fragments: KQ k16 steps of 1 KB
-        constexpr int jstep = 8 * KQ * 1024;      // bytes between column tiles wc and wc + 8
+        const __amdgpu_buffer_rsrc_t bhr = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(Wfhi), 0, 16 * KQL * K * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t blr = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(Wflo), 0, 16 * KQL * K * 2, 0x00020000);
+        const int btile = wc * (KQL * 1024);      // bytes of a column tile's fragments: KQ k16 steps of 1 KB
+        constexpr int jstep = 8 * KQL * 1024;     // bytes between column tiles wc and wc + 8
         f16x8 bh0[2], bl0[2], bh1[2], bl1[2];
 #define CHIP_LB(R, B, Q, J) B[J] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(R, lane16, btile + (J) * jstep + (Q) * 1024, 0));
 #define CHIP_BLOAD(BH, BL, Q) { CHIP_LB(bhr, BH, Q, 0) CHIP_LB(blr, BL, Q, 0) CHIP_LB(bhr, BH, Q, 1) CHIP_LB(blr, BL, Q, 1) }
         CHIP_BLOAD(bh0, bl0, 0)
-        __syncthreads();                          // stages 0 .. NSLOT - 1 of layer li published
+        __syncthreads();                          // stages 0 .. NSLOT - 1 of the layer published
         CHIP_TS()
 
-        // ------------------------------------------------------------------ 1 x 1 convolution of layer li
         // (a zero the compiler cannot form early: as plain constants the 96 clears were hoisted above the barrier into the
         //  depthwise phase, where the accumulators' registers are what its 96 results live in - 43 spills)
         float zero;
@@ -256,7 +240,7 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         const char* abase = sm + ((FROM) < NSLOT ? (FROM) : (FROM) - NSLOT) * kChipSlotBytes;             \
         CHIP_LAH(ah0, 0, 0) CHIP_LAL(al0, 0, 0) CHIP_LAH(ah1, 0, 1) CHIP_LAL(al1, 0, 1)                   \
         _Pragma("nounroll") for (int kk = (FROM); kk < (TO); ++kk) {                                      \
-            const int q1 = 2 * kk + 1, q2 = 2 * kk + 2 < KQ ? 2 * kk + 2 : 0;     /* (the last stage re-reads step 0: unused) */ \
+            const int q1 = 2 * kk + 1, q2 = 2 * kk + 2 < KQL ? 2 * kk + 2 : 0;    /* (the last stage re-reads step 0: unused) */ \
             const char* const anext = sm + (kk + 1 < (TO) ? (kk + 1 < NSLOT ? kk + 1 : kk + 1 - NSLOT) : (kk < NSLOT ? kk : kk - NSLOT)) * kChipSlotBytes; \
             CHIP_STEP(0, ah0, al0, bh0, bl0, CHIP_LB(bhr, bh1, q1, 0), CHIP_LB(blr, bl1, q1, 0), CHIP_LB(bhr, bh1, q1, 1),  \
                       CHIP_LB(blr, bl1, q1, 1), CHIP_LAH(ah2, 0, 2), CHIP_LAL(al2, 0, 2))                 \
@@ -269,9 +253,9 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
             CHIP_STEP(2, ah2, al2, bh1, bl1, CHIP_LAH(ah1, 0, 1), CHIP_LAL(al1, 0, 1), CHIP_NOP, CHIP_NOP, CHIP_NOP, CHIP_NOP) \
         }                                                                                                 \
     }
-        CHIP_STAGES(0, NPEND)
+        CHIP_STAGES(0, NP)
         CHIP_TS()
-        if constexpr (NPEND > 0) {
+        if constexpr (NP > 0) {
             __syncthreads();                      // every wave has read stages 0 .. NPEND - 1: their slots are free
             CHIP_TS()
             if (wc >= 8 - NPEND) {
@@ -286,9 +270,9 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         // ... and the other waves wait for them HERE, not at stage NSLOT: a wave that publishes beside a neighbour's
         // back-to-back MFMAs gets an LDS write through every ~90 cycles (9 000 cycles for its 96, measured) and everyone
         // waited for it ten stages later; with the whole workgroup at the barrier the 96 writes take ~1 000
-        if constexpr (NPEND > 0) __syncthreads();  // pending stages published
+        if constexpr (NP > 0) __syncthreads();    // pending stages published
         CHIP_TS()
-        CHIP_STAGES(NPEND, 16)
+        CHIP_STAGES(NP, NS)
         CHIP_TS()
 #undef CHIP_STAGES
 #undef CHIP_STEP
@@ -299,15 +283,18 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
 #undef CHIP_MF
 #undef CHIP_SB
 #undef CHIP_NOP
-        if (li + 1 == nl) break;
+    };
 
-        // ------------------------------------------------------------------ depthwise of layer li + 1 on the accumulators
-        const __amdgpu_buffer_rsrc_t taps = CHIP_TAPS_RSRC(chain_ptr<float>(0, li + 1));
-        const __amdgpu_buffer_rsrc_t pur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(chain_ptr<float>(4, li)), 0, K * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t pbr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(chain_ptr<float>(5, li)), 0, K * 4, 0x00020000);
+    // ---------------------------------------------------------------------- the step from a layer's product to the next layer's
+    // A operand: epilogue (U, B of the layer), the half-wave swap, the depthwise of the next layer (TAPS) on the accumulators,
+    // the publication into the ring
+    auto next_layer = [&](const float* const taps_w, const float* const pu, const float* const pb) __attribute__((always_inline)) {
+        const __amdgpu_buffer_rsrc_t taps = CHIP_TAPS_RSRC(taps_w);
+        const __amdgpu_buffer_rsrc_t pur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pu), 0, K * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t pbr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pb), 0, K * 4, 0x00020000);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int st = j ? wc + 8 : wc;       // stage of layer li + 1 = column block of layer li
+            const int st = j ? wc + 8 : wc;       // stage of the next layer = column block of this one
             const float u = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pur, c4, 128 * st, 0));
             const float b = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pbr, c4, 128 * st, 0));
             // stacked map row R = 8 i + 2 (r >> 2) + owner half, x = r & 3.  Pair q (rows 2 q, 2 q + 1) of windows 0-1 is
@@ -341,6 +328,77 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         __syncthreads();                          // every wave has read every stage: the ring is free for this layer's tile
         CHIP_TS()
         CHIP_PUBLISH()
+    };
+
+    const long long rows_left = M - m0;
+    const unsigned tile_bytes = (unsigned)(rows_left < 96 ? rows_left : 96) * (K * 4);
+    if constexpr (PW7) {
+        // ------------------------------------------------------------------ pointwise 7 on the depthwise-7 planes
+        // The 8 ring slots of its A operand are one run of 8 x 12 416 B = 97 x 1 KB pieces; piece n is DMA instruction n / 8 of
+        // wave n % 8, lane l of it fills the 16 bytes at 16 (64 n + l).  Those are (stage, half, LDS row rho, slot) of the ring
+        // image, and slot p of row rho holds channels 8 (p ^ key) .. + 7, key = (rho >> 2) & 3, of tile row rho = 24 w + 4 oy + ox:
+        // window w of the tile.  The resource covers the tile's windows in the batch only: rows past it read as zero, and
+        // the 64 bytes in front of row 48 (the skew), and the lo halves in the plain-f16 mode, take an offset outside it.
+        const long long w0 = m0 / 24, wleft = M / 24 - w0;
+        const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<char*>(reinterpret_cast<const char*>(X)) + (size_t)w0 * kDw7PlaneBytes, 0,
+            (unsigned)(wleft < 4 ? wleft : 4) * kDw7PlaneBytes, 0x00020000);
+        constexpr int kPieces = 8 * kChipSlotBytes / 1024;
+        static_assert(kPieces * 1024 == 8 * kChipSlotBytes && 8 * kChipSlotBytes <= NSLOT * kChipSlotBytes, "whole pieces");
+#pragma unroll
+        for (int t = 0; t < (kPieces + 7) / 8; ++t) {
+            const int n = 8 * t + wc;
+            if (n >= kPieces) break;                                  // (wave-uniform)
+            const int c = 64 * n + lane;                              // 16-byte unit of the 8 slots
+            const int s = c / (kChipSlotBytes / 16), cs = c - s * (kChipSlotBytes / 16);
+            const int h = cs >= kChipHalfBytes / 16 ? 1 : 0;
+            const int o = (cs - h * (kChipHalfBytes / 16)) * 16;      // byte of the half
+            const bool skew = o >= 48 * 64 && o < 49 * 64;
+            const int rho = o < 48 * 64 ? o >> 6 : (o - 64) >> 6;
+            const int p = (o >> 4) & 3, w = rho / 24;
+            const unsigned src = (unsigned)(w * kDw7PlaneBytes + s * (kDw7PlaneBytes / 8) + h * (kDw7PlaneBytes / 16) +
+                                            (rho - 24 * w) * 64 + ((p ^ ((rho >> 2) & 3)) << 4));
+            const unsigned off = skew || (PLAIN && h) ? 0x7ffffff0u : src;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(pr, (__attribute__((address_space(3))) void*)(sm + n * 1024), 16, off, 0, 0, 0);
+        }
+        // this wave's pieces have landed.  (All of them: a B load behind a piece cannot be waited for alone - loads complete
+        // in order - and the K loop's first step waits for B fragments requested in front of its barrier)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        CHIP_TS()
+        k_loop(std::integral_constant<int, 16>{}, ch.w7hi, ch.w7lo);
+        next_layer(ch.dw_w[0], ch.u7, ch.b7);
+    } else {
+        // ------------------------------------------------------------------ layer 0: its depthwise reads the run's input
+        // through a buffer resource that covers exactly this tile's valid rows: a row past the end of the batch (tail tile)
+        // reads as zero, with no clamping code, and every load is resource + one per-lane offset register + a scalar row offset
+        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X) + (size_t)m0 * K, 0, tile_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t taps0 = CHIP_TAPS_RSRC(ch.dw_w[0]);
+        const unsigned xo = (48u * fh * K) * 4 + c4;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int st = j ? wc + 8 : wc;
+            v2f in2[6][4];
+#pragma unroll
+            for (int y = 0; y < 6; ++y)
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {
+                    in2[y][x].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, xo, ((4 * y + x) * K + 32 * st) * 4, 0));
+                    in2[y][x].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, xo, ((24 + 4 * y + x) * K + 32 * st) * 4, 0));
+                }
+            if (j == 0) CHIP_DW(0, st, taps0)
+            else CHIP_DW(1, st, taps0)
+            CHIP_TS()
+            __builtin_amdgcn_sched_barrier(0);    // (the second block's 48 loads hoisted over the first's sums cost a spill)
+        }
+        CHIP_PUBLISH()
+    }
+
+    for (int li = 0; li < nl; ++li) {
+        // ------------------------------------------------------------------ 1 x 1 convolution of layer li
+        k_loop(std::integral_constant<int, KQ>{}, chain_ptr<_Float16>(2, li), chain_ptr<_Float16>(3, li));
+        if (li + 1 == nl) break;
+        // ------------------------------------------------------------------ depthwise of layer li + 1 on the accumulators
+        next_layer(chain_ptr<float>(0, li + 1), chain_ptr<float>(4, li), chain_ptr<float>(5, li));
     }
 #undef CHIP_DW
 #undef CHIP_PUBLISH
@@ -439,9 +497,16 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
 
 constexpr int kMaxDevicesChip = 64;
 
-template <bool PLAIN, bool NDW, bool PLANES = false>
-void launch_chip(const float* in, float* out, const SepLayer* L, int nl, long long M, const float* ndw_w, hipStream_t stream) {
+template <bool PLAIN, bool NDW, bool PLANES = false, bool PW7 = false>
+void launch_chip(const float* in, float* out, const SepLayer* L, int nl, long long M, const float* ndw_w, hipStream_t stream,
+                 const SepLayer* L7 = nullptr) {
     ChipChain ch{};
+    if (L7) {
+        ch.w7hi = static_cast<const _Float16*>(L7->pw_fhi);
+        ch.w7lo = static_cast<const _Float16*>(L7->pw_flo);
+        ch.u7 = L7->pw_u;
+        ch.b7 = L7->pw_b;
+    }
     for (int i = 0; i < nl; ++i) {
         ch.dw_w[i] = dw_w_of(L[i]);
         ch.dw_b[i] = dw_b_of(L[i]);
@@ -458,7 +523,7 @@ void launch_chip(const float* in, float* out, const SepLayer* L, int nl, long lo
     int dev = 0;
     (void)hipGetDevice(&dev);
     std::call_once(once[dev & (kMaxDevicesChip - 1)], [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_chip_kernel<PLAIN, NSLOT, false, NDW, PLANES>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_chip_kernel<PLAIN, NSLOT, false, NDW, PLANES, PW7>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     });
     const long long tiles = (M + 95) / 96;
@@ -466,29 +531,30 @@ void launch_chip(const float* in, float* out, const SepLayer* L, int nl, long lo
 #ifdef BD_KERNEL_TRACE      // developer build only: BD_CHIP_TUNE = policy under test; BD_WS_TRACE=7 stamps workgroup 0
     if (const char* tn = getenv("BD_CHIP_TUNE")) tune = atoi(tn);
     const char* tr = getenv("BD_WS_TRACE");
-    if (tr && tr[0] == '7' && !PLANES) {
+    if (tr && tr[0] == '7') {
         static unsigned long long* dbg = nullptr;
         static int shots = 0;
         if (!dbg) (void)hipMalloc(&dbg, 128 * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_chip_kernel<PLAIN, NSLOT, true, NDW>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_chip_kernel<PLAIN, NSLOT, true, NDW, PLANES, PW7>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         (void)hipMemsetAsync(dbg, 0, 128 * 8, stream);
-        hipLaunchKernelGGL((sep_chip_kernel<PLAIN, NSLOT, true, NDW>), dim3((unsigned)tiles), dim3(512), lds, stream, ch, in, out, nl,
+        hipLaunchKernelGGL((sep_chip_kernel<PLAIN, NSLOT, true, NDW, PLANES, PW7>), dim3((unsigned)tiles), dim3(512), lds, stream, ch, in, out, nl,
                            M, L[0].range_flag, dbg, tune);
         (void)hipStreamSynchronize(stream);
         unsigned long long h[128];
         (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
         if (++shots == 8)
             for (int w = 0; w < 2; ++w) {
-                fprintf(stderr, "[trace] on-chip run of %d layers, wave %d: cycles between stamps (start | dw0 j0 j1 | per layer: B1, stages 0-2, B2, pend, "
-                                "B3, stages 3-15, [dw j0, dw j1, B4] | stores):", nl, w ? 5 : 0);
+                fprintf(stderr, "[trace] on-chip run of %d layers%s, wave %d: cycles between stamps (start | %s | per layer: B1, stages 0-2, B2, pend, "
+                                "B3, stages 3-15, [dw j0, dw j1, B4] | stores):", nl, PW7 ? " + pointwise 7" : "", w ? 5 : 0,
+                        PW7 ? "DMA, B1, -, -, -, stages 0-7, dw j0, dw j1, B4" : "dw0 j0 j1");
                 for (int i = 1; i < 64 && h[w * 64 + i]; ++i) fprintf(stderr, " %llu", h[w * 64 + i] - h[w * 64 + i - 1]);
                 fprintf(stderr, "\n");
             }
         return;
     }
 #endif
-    hipLaunchKernelGGL((sep_chip_kernel<PLAIN, NSLOT, false, NDW, PLANES>), dim3((unsigned)tiles), dim3(512), lds, stream, ch, in, out, nl, M,
+    hipLaunchKernelGGL((sep_chip_kernel<PLAIN, NSLOT, false, NDW, PLANES, PW7>), dim3((unsigned)tiles), dim3(512), lds, stream, ch, in, out, nl, M,
                        L[0].range_flag, (unsigned long long*)nullptr, tune);
 }
 
@@ -522,6 +588,30 @@ bool launch_separable_chip(const float* in, float* out, int windows, const SepLa
         if (next) launch_chip<false, true>(in, out, L, nl, M, nw, stream);
         else launch_chip<false, false>(in, out, L, nl, M, nw, stream);
     }
+    return true;
+}
+
+// Pointwise 7 (L7) on the depthwise-7 planes sep_mid_kernel<.., DW7OUT> writes (kDw7PlaneBytes per window), then the run L[0 ..
+// nl - 1] and next's depthwise, out = the planes septail.hip reads: launch_separable_chip(.., next, planes = true) with the
+// run's first input computed on the CU.  Would it run?
+bool separable_chip_pw7_supported(const SepLayer& L7, const SepLayer* L, int nl, const SepLayer& next, int windows) {
+    if (windows <= 0 || (long long)windows * 24 >= (1LL << 31) || nl < 1 || nl > kChipMaxLayers) return false;
+    if (L7.cin != 256 || L7.cout != 512 || L7.h_out != 6 || L7.w_out != 4 || L7.pw_mode == 0 || !L7.pw_fhi || !L7.pw_flo)
+        return false;
+    for (int i = 0; i < nl; ++i)
+        if (L[i].stride != 1 || L[i].cin != 512 || L[i].cout != 512 || L[i].h_out != 6 || L[i].w_out != 4 ||
+            L[i].pw_mode != L7.pw_mode || dw_b_of(L[i]) != dw_w_of(L[i]) + 9 * 512)
+            return false;
+    return next.stride == 2 && next.cin == 512 && dw_b_of(next) == dw_w_of(next) + 9 * 512;
+}
+
+bool launch_separable_chip_pw7(const void* in, float* out, int windows, const SepLayer& L7, const SepLayer* L, int nl,
+                               const SepLayer& next, hipStream_t stream) {
+    if (!separable_chip_pw7_supported(L7, L, nl, next, windows) || in == out) return false;
+    const float* const X = static_cast<const float*>(in);
+    const long long M = (long long)windows * 24;
+    if (L7.pw_mode == 2) launch_chip<true, true, true, true>(X, out, L, nl, M, dw_w_of(next), stream, &L7);
+    else launch_chip<false, true, true, true>(X, out, L, nl, M, dw_w_of(next), stream, &L7);
     return true;
 }
 

@@ -46,6 +46,11 @@ constexpr int kSlot7 = 2 * kHalf7;              // 6144
 constexpr int kOffA7 = 8 * kSlotA;              // A7 behind the ring A5 and A6 share
 constexpr int kMidLds = kOffA7 + 8 * kSlot7 + 1024;   // 149504 (+ 1 KB: the second row tile of layer 7 reads 16 rows past a stage)
 static_assert(kMidLds <= 160 * 1024, "one workgroup per CU");
+// DW7OUT: a wave's stage of a window's depthwise-7 planes ([hi, lo][24 rows][64 B], kDw7PlaneBytes / 8) is assembled behind
+// the ring, one area per wave, and leaves at 16 bytes per lane
+constexpr int kStage7 = kDw7PlaneBytes / 8;     // 3072
+constexpr int kMidLdsDw7 = kOffA7 + 8 * kStage7;       // 123904
+static_assert(kStage7 == 2 * 24 * 64, "[hi, lo][24 rows][32 channels] f16");
 
 struct MidArgs {
     const _Float16 *w5h, *w5l, *w6h, *w6l, *w7h, *w7l;     // MFMA B-fragment order [cout / 32][cin / 16][64][8]
@@ -57,7 +62,10 @@ struct MidArgs {
 #define MID_LD32(R, VOFF, SOFF) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(R, VOFF, SOFF, 0))
 #define MID_LD128(R, VOFF, SOFF) __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(R, VOFF, SOFF, 0))
 
-template <bool PLAIN, bool TRACE>
+// DW7OUT: the kernel ends at depthwise 7.  Y is then the split-f16 depthwise-7 output, per window [stage 0..7][hi, lo][24 rows]
+// [32 channels] (kDw7PlaneBytes; row 4 oy + ox, only the hi planes in the plain-f16 mode), which sep_chip_kernel<.., PW7> reads
+// as pointwise 7's A operand; windows go one at a time and layer 7's K loop, B ring and A7 area are not compiled.
+template <bool PLAIN, bool TRACE, bool DW7OUT = false>
 __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const float* __restrict__ X, float* __restrict__ Y, int windows,
                                                           unsigned* __restrict__ range_flag, unsigned long long* __restrict__ dbg) {
     extern __shared__ __attribute__((aligned(16))) char sm[];
@@ -298,6 +306,7 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
             int wbl = wb7;
             asm volatile("" : "+v"(wbl));
             char* const slot = sm + kOffA7 + wc * kSlot7;
+            char* const stg = sm + kOffA7 + wc * kStage7;     // DW7OUT: this wave's stage of the window's planes
             // output (oy, ox = 2 fh + j) reads map rows 2 oy + kh, columns 2 ox + kw = 4 fh + 2 j + kw; SAME padding of a
             // stride-2 layer: one row / column BEHIND the map (row 12; column 8 = the upper half's right halo = 0)
             // two output rows (oy, oy + 3) per v_pk_fma_f32: their input rows 2 oy + kh and 2 oy + kh + 6 are one row pair
@@ -318,12 +327,34 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
                         const int oyw = oy + 3 * w;
                         const float o = fmaxf(w ? sacc.y : sacc.x, 0.0f);
                         MID_SPLIT(o, pk)
-                        // row 24 HALF + 4 oy + 2 fh + j of the 48-row stage: key (row >> 2) & 3 = (6 HALF + oy) & 3
-                        char* const p_ = slot + (wbl ^ (((6 * HALF + oyw) & 3) << 4)) + (24 * HALF + 4 * oyw + j) * 64;
-                        *reinterpret_cast<unsigned short*>(p_) = (unsigned short)pk;
-                        *reinterpret_cast<unsigned short*>(p_ + kHalf7) = (unsigned short)(pk >> 16);
+                        if constexpr (DW7OUT) {
+                            // row 4 oy + 2 fh + j of the stage, channel frow: plain [row][32] f16 (the reader swizzles)
+                            char* const p_ = stg + (4 * oyw + 2 * fh + j) * 64 + 2 * frow;
+                            *reinterpret_cast<unsigned short*>(p_) = (unsigned short)pk;
+                            if constexpr (!PLAIN) *reinterpret_cast<unsigned short*>(p_ + kStage7 / 2) = (unsigned short)(pk >> 16);
+                        } else {
+                            // row 24 HALF + 4 oy + 2 fh + j of the 48-row stage: key (row >> 2) & 3 = (6 HALF + oy) & 3
+                            char* const p_ = slot + (wbl ^ (((6 * HALF + oyw) & 3) << 4)) + (24 * HALF + 4 * oyw + j) * 64;
+                            *reinterpret_cast<unsigned short*>(p_) = (unsigned short)pk;
+                            *reinterpret_cast<unsigned short*>(p_ + kHalf7) = (unsigned short)(pk >> 16);
+                        }
                     }
                 }
+            if constexpr (DW7OUT) {
+                // the wave's stage, as assembled above (LDS requests of one wave complete in order: no barrier), to memory at 16
+                // bytes per lane.  (A 16-byte store whose data registers are overwritten two vector instructions later has been
+                // seen to store the new values - DESIGN.md 10: the store and three wait states behind it are one asm statement)
+                typedef __attribute__((address_space(1))) char* gchar;
+                typedef float v4f __attribute__((ext_vector_type(4)));
+                asm volatile("" ::: "memory");
+                const gchar dst = (gchar)Y + (size_t)win * kDw7PlaneBytes + wc * kStage7 + lane * 16;
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    if (PLAIN && (t == 2 || (t == 1 && lane >= 32))) continue;    // hi plane only: its 1536 bytes
+                    const v4f v = *reinterpret_cast<const v4f*>(stg + t * 1024 + lane * 16);
+                    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 2" : : "v"(dst + t * 1024), "v"(v) : "memory");
+                }
+            }
         }
         if constexpr (LAST) {
 #pragma unroll
@@ -392,7 +423,10 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
     const int w_begin = (int)(((long long)blockIdx.x * windows) / gridDim.x);
     const int w_end = (int)(((long long)(blockIdx.x + 1) * windows) / gridDim.x);
     if (w_begin < w_end) fetch_window(w_begin);
-    for (int win = w_begin; win < w_end; win += 2) {
+    if constexpr (DW7OUT) {
+        for (int win = w_begin; win < w_end; ++win)
+            window_to_a7(std::integral_constant<int, 0>{}, std::false_type{}, win, win + 1 < w_end ? win + 1 : -1);
+    } else for (int win = w_begin; win < w_end; win += 2) {
         const bool two = win + 1 < w_end;
         if (two) {
             window_to_a7(std::integral_constant<int, 0>{}, std::false_type{}, win, win + 1);
@@ -412,8 +446,9 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
 #undef MID_HALO
 }
 
-template <bool PLAIN>
+template <bool PLAIN, bool DW7OUT>
 void launch_mid(const float* in, float* out, int windows, const SepLayer& L5, const SepLayer& L6, const SepLayer& L7, hipStream_t stream) {
+    constexpr int lds = DW7OUT ? kMidLdsDw7 : kMidLds;
     MidArgs a{};
     a.w5h = static_cast<const _Float16*>(L5.pw_fhi);
     a.w5l = static_cast<const _Float16*>(L5.pw_flo);
@@ -430,7 +465,7 @@ void launch_mid(const float* in, float* out, int windows, const SepLayer& L5, co
     int dev = 0;
     (void)hipGetDevice(&dev);
     std::call_once(once[dev & 63], [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_mid_kernel<PLAIN, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMidLds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_mid_kernel<PLAIN, false, DW7OUT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     });
     int grid = cu_count();
     if (grid > windows) grid = windows;
@@ -440,25 +475,36 @@ void launch_mid(const float* in, float* out, int windows, const SepLayer& L5, co
         static unsigned long long* dbg = nullptr;
         static int shots = 0;
         if (!dbg) (void)hipMalloc(&dbg, 128 * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_mid_kernel<PLAIN, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMidLds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_mid_kernel<PLAIN, true, DW7OUT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         (void)hipMemsetAsync(dbg, 0, 128 * 8, stream);
-        hipLaunchKernelGGL((sep_mid_kernel<PLAIN, true>), dim3(grid), dim3(512), kMidLds, stream, a, in, out, windows, L5.range_flag, dbg);
+        hipLaunchKernelGGL((sep_mid_kernel<PLAIN, true, DW7OUT>), dim3(grid), dim3(512), lds, stream, a, in, out, windows, L5.range_flag, dbg);
         (void)hipStreamSynchronize(stream);
         unsigned long long h[128];
         (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
         if (++shots == 8)
             for (int w = 0; w < 2; ++w) {
-                fprintf(stderr, "[trace] mid run, wave %d: cycles between stamps (per window: A5+B1, K5, dw6+Bx, publish+B2, K6, dw7+B3; per pair: K7, stores):", w ? 5 : 0);
+                fprintf(stderr, "[trace] mid run, wave %d: cycles between stamps (per window: A5+B1, K5, dw6+Bx, publish+B2, K6, %s):", w ? 5 : 0,
+                        DW7OUT ? "dw7 + its planes stored" : "dw7+B3; per pair: K7, stores");
                 for (int i = 1; i < 64 && h[w * 64 + i]; ++i) fprintf(stderr, " %llu", h[w * 64 + i] - h[w * 64 + i - 1]);
                 fprintf(stderr, "\n");
             }
         return;
     }
 #endif
-    hipLaunchKernelGGL((sep_mid_kernel<PLAIN, false>), dim3(grid), dim3(512), kMidLds, stream, a, in, out, windows, L5.range_flag,
+    hipLaunchKernelGGL((sep_mid_kernel<PLAIN, false, DW7OUT>), dim3(grid), dim3(512), lds, stream, a, in, out, windows, L5.range_flag,
                        (unsigned long long*)nullptr);
 }
 
+}  // namespace
+
+namespace {
+bool mid_shapes_ok(const SepLayer& L5, const SepLayer& L6, const SepLayer& L7) {
+    if (L5.cin != 128 || L5.cout != 256 || L5.h_out != 12 || L5.w_out != 8 || L6.cin != 256 || L6.cout != 256 || L6.stride != 1 ||
+        L6.h_out != 12 || L6.w_out != 8 || L7.cin != 256 || L7.cout != 512 || L7.stride != 2 || L7.h_out != 6 || L7.w_out != 4)
+        return false;
+    if (L5.pw_mode == 0 || L6.pw_mode != L5.pw_mode || L7.pw_mode != L5.pw_mode) return false;
+    return dw_b_of(L6) == dw_w_of(L6) + 9 * 256 && dw_b_of(L7) == dw_w_of(L7) + 9 * 256;
+}
 }  // namespace
 
 // Pointwise 5 -> layer 6 -> depthwise 7 -> pointwise 7 as one launch: in = depthwise-5 output [windows][12][8][128] (what
@@ -466,14 +512,22 @@ void launch_mid(const float* in, float* out, int windows, const SepLayer& L5, co
 // when the shapes or the table layouts are not the ones the kernel is built for.
 bool launch_separable_mid(const float* in, float* out, int windows, const SepLayer& L5, const SepLayer& L6, const SepLayer& L7,
                           hipStream_t stream) {
-    if (windows <= 0 || in == out) return false;
-    if (L5.cin != 128 || L5.cout != 256 || L5.h_out != 12 || L5.w_out != 8 || L6.cin != 256 || L6.cout != 256 || L6.stride != 1 ||
-        L6.h_out != 12 || L6.w_out != 8 || L7.cin != 256 || L7.cout != 512 || L7.stride != 2 || L7.h_out != 6 || L7.w_out != 4)
-        return false;
-    if (L5.pw_mode == 0 || L6.pw_mode != L5.pw_mode || L7.pw_mode != L5.pw_mode) return false;
-    if (dw_b_of(L6) != dw_w_of(L6) + 9 * 256 || dw_b_of(L7) != dw_w_of(L7) + 9 * 256) return false;
-    if (L5.pw_mode == 2) launch_mid<true>(in, out, windows, L5, L6, L7, stream);
-    else launch_mid<false>(in, out, windows, L5, L6, L7, stream);
+    if (windows <= 0 || in == out || !mid_shapes_ok(L5, L6, L7)) return false;
+    if (L5.pw_mode == 2) launch_mid<true, false>(in, out, windows, L5, L6, L7, stream);
+    else launch_mid<false, false>(in, out, windows, L5, L6, L7, stream);
+    return true;
+}
+
+bool separable_mid_planes_supported(const SepLayer& L5, const SepLayer& L6, const SepLayer& L7) { return mid_shapes_ok(L5, L6, L7); }
+
+// The same launch ending at depthwise 7: out = its split-f16 output, kDw7PlaneBytes per window (sep_mid_kernel<.., DW7OUT>),
+// what launch_separable_chip_pw7 reads.
+bool launch_separable_mid_planes(const float* in, void* out, int windows, const SepLayer& L5, const SepLayer& L6, const SepLayer& L7,
+                                 hipStream_t stream) {
+    if (windows <= 0 || in == out || !mid_shapes_ok(L5, L6, L7)) return false;
+    float* const Y = static_cast<float*>(out);
+    if (L5.pw_mode == 2) launch_mid<true, true>(in, Y, windows, L5, L6, L7, stream);
+    else launch_mid<false, true>(in, Y, windows, L5, L6, L7, stream);
     return true;
 }
 
