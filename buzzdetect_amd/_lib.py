@@ -161,6 +161,24 @@ PCM_PROTOTYPES = {
                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
+HEAD_ABI_VERSION = 1
+HEAD_MAX_LAYERS = 8
+HEAD_MAX_WIDTH = 2048
+HEAD_ACTIVATIONS = {"linear": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "softmax": 4}
+
+
+class bd_head_layer(C.Structure):
+    _fields_ = [("kernel", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float)), ("n_in", C.c_int32), ("n_out", C.c_int32),
+                ("activation", C.c_int32), ("reserved", C.c_int32)]
+
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_head.h
+HEAD_PROTOTYPES = {
+    "bd_head_abi_version": (C.c_int, []),
+    "bd_head_attach": (C.c_int, [C.c_void_p, C.POINTER(bd_head_layer), C.c_int32]),
+    "bd_head_outputs": (C.c_int, [C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -192,7 +210,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         except (RuntimeError, OSError, subprocess.CalledProcessError) as exc:
             raise RuntimeError(f"{path} is older than its sources and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
+            + list(HEAD_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -202,6 +221,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: FLAC ABI version {lib.bd_flac_abi_version()} != {FLAC_ABI_VERSION}; rebuild")
     if lib.bd_pcm_abi_version() != PCM_ABI_VERSION:
         raise RuntimeError(f"{path}: PCM ABI version {lib.bd_pcm_abi_version()} != {PCM_ABI_VERSION}; rebuild")
+    if lib.bd_head_abi_version() != HEAD_ABI_VERSION:
+        raise RuntimeError(f"{path}: head ABI version {lib.bd_head_abi_version()} != {HEAD_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

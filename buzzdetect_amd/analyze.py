@@ -51,14 +51,18 @@ def search_audio(dir_audio: str) -> List[str]:
 
 def analyze(modelname: str = "model_general_v3", classes_out="all", precision: Optional[float] = None,
             framehop_prop: float = 1, chunklength: float = 200, dir_audio: str = "audio_in",
-            dir_out: Optional[str] = None, embeddername: str = "yamnet_k2", engine=None,
+            dir_out: Optional[str] = None, embeddername: Optional[str] = None, engine=None,
             rank: Optional[int] = None, world_size: Optional[int] = None, analyzers_gpu: int = 2,
             n_streamers: Optional[int] = None, engines: Optional[list] = None,
             gather_logits: bool = False, analyzers_cpu: int = 0, stream_buffer_depth: Optional[int] = None,
             verbosity_print: Optional[str] = None, verbosity_log: Optional[str] = None, log_progress: bool = False,
-            event_stopanalysis=None) -> AnalyzeReport:
+            event_stopanalysis=None, dir_models: Optional[str] = None) -> AnalyzeReport:
     """Analyse every recording with one of ``EXTENSIONS`` under ``dir_audio``; write ``<ident>_buzzdetect.csv`` under ``dir_out``.
 
+    ``modelname`` is a directory of that name (``weights.load_head``: under ``dir_models`` if given, else ``models/`` in the
+    working directory, ``$BUZZDETECT_MODELS_DIR``, the packaged overlay); its ``config_model.json`` gives the classes, the
+    decimals of the result files (``digits_results``) and the embedder (``embeddername=None``: the model's), its
+    ``tests/metrics.csv`` the detection threshold.
     ``classes_out`` / ``precision`` choose activations vs detections exactly as in the reference;
     ``rank`` / ``world_size`` default to the torch.distributed environment (one process per GPU);
     ``analyzers_gpu`` analyzer threads (each with its own engine and HIP stream) are fed by ``n_streamers`` reader
@@ -92,7 +96,7 @@ def analyze(modelname: str = "model_general_v3", classes_out="all", precision: O
     try:
         return _analyze(modelname, classes_out, precision, framehop_prop, chunklength, dir_audio, dir_out, embeddername,
                         engine, rank, world_size, dist, analyzers_gpu, n_streamers, engines, gather_logits, analyzers_cpu,
-                        stream_buffer_depth, event_stopanalysis)
+                        stream_buffer_depth, event_stopanalysis, dir_models)
     finally:
         for h in handlers:
             _log.removeHandler(h)
@@ -135,22 +139,33 @@ def _attach_log_handlers(dir_out: str, verbosity_print, verbosity_log, log_progr
 
 def _analyze(modelname, classes_out, precision, framehop_prop, chunklength, dir_audio, dir_out, embeddername, engine, rank,
              world_size, dist, analyzers_gpu, n_streamers, engines, gather_logits, analyzers_cpu, stream_buffer_depth,
-             event_stopanalysis) -> AnalyzeReport:
+             event_stopanalysis, dir_models=None) -> AnalyzeReport:
+    from . import weights
     from .engine import HipEngine, hop_samples, patch_step
     if analyzers_cpu:
         _log.debug(f"analyzers_cpu={analyzers_cpu} ignored: the MI355X engine has no CPU path")
 
-    framelength_s, digits_time, digits_results = 0.96, 2, 2
+    framelength_s, digits_time = 0.96, 2
     framehop_s = framelength_s * framehop_prop
     chunklength = framing.round_chunklength(chunklength, framelength_s, digits_time)
     if engines:
         engine = None
-    probe = engine or (engines[0] if engines else HipEngine(embeddername=embeddername, modelname=modelname))
+    probe = engine or (engines[0] if engines else None)
+    # what the reference takes from the model (config_model.json / BaseModel): classes, digits_results, the embedder's name
+    head = getattr(probe, "head", None) if probe is not None else weights.load_head(modelname, dir_models)
+    if head is None:                                   # an engine without a classifier: the named model's settings
+        head = weights.load_head(modelname, dir_models)
+    digits_results = head.digits_results
+    if embeddername is None:
+        embeddername = head.embeddername
+    if probe is None:
+        probe = HipEngine(embeddername=embeddername, head=head)
     classes = probe.classes
     device_index = probe.device_index
     if classes_out == "all":
         classes_out = list(classes)
-    threshold = None if precision is None else results.threshold_for_precision(modelname, precision)
+    threshold = None if precision is None else results.threshold_for_precision(modelname, precision,
+                                                                                  metrics_path=head.metrics_path)
 
     # The manifest locks a results folder to one set of settings.  Rank 0 writes (or checks) it; the others wait for
     # that, then every rank validates the folder for itself, so a conflict stops ALL ranks before any row is written.
@@ -186,7 +201,7 @@ def _analyze(modelname, classes_out, precision, framehop_prop, chunklength, dir_
         def make_engine():        # the probe engine serves the first analyzer thread; the others build their own
             if first:
                 return first.pop()
-            return HipEngine(embeddername=embeddername, modelname=modelname, device=device_index)
+            return HipEngine(embeddername=embeddername, head=head, device=device_index)
 
     readers = n_streamers if n_streamers else STREAMERS_PER_ANALYZER * analyzers
     common = dict(make_engine=make_engine, classes=classes, framehop_s=framehop_s, hop=hop_samples(framehop_s),

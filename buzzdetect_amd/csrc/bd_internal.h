@@ -195,4 +195,17 @@ void launch_pool_head(const float* act, int windows, const float* head_wt, const
 void launch_head(const float* pooled, int windows, const float* head_wt, const float* head_b, int n_classes,
                  float* logits, hipStream_t stream);
 
+// One Dense layer of an attached head stack (headmlp.hip, include/buzzdetect_head.h)
+struct DenseLayer {
+    int k, n;            // inputs, outputs
+    int act;             // BD_HEAD_*
+    const float* wfrag;  // the kernel in the f32 matrix instruction's B-fragment order, zero-padded (dense_pack_weights)
+    const float* bias;   // [n]
+};
+size_t dense_packed_floats(int k, int n);
+void dense_pack_weights(const float* kernel, int k, int n, float* dst);      // host: [k][n] -> fragment order
+// C[windows][ldc] (columns < n) = act(A[windows][lda] (columns < k) W + b); lda >= round_up(k, 32), A != C
+void launch_dense(const float* A, int lda, int windows, const DenseLayer& L, float* C, int ldc, hipStream_t stream);
+void launch_softmax_rows(const float* x, int ldx, float* y, int windows, int n, hipStream_t stream);  // x [windows][ldx] -> y [windows][n]
+
 }  // namespace bd

@@ -13,6 +13,8 @@
 
 #include "bd_internal.h"
 
+#include "../../include/buzzdetect_head.h"
+
 namespace {
 
 thread_local std::string g_error;
@@ -77,6 +79,9 @@ struct bd_engine {
     bd::SepLayer sep[13];
     const float* head_wt = nullptr;   // [n_classes][1024]
     const float* head_b = nullptr;
+    // a dense stack in place of that head (bd_head_attach): n_classes is then its last width
+    std::vector<bd::DenseLayer> stack;
+    float* d_stack = nullptr;         // one allocation for the stack's packed kernels and biases
     // resampler: the filters of every (up, down) pair used so far, kept on the device until bd_destroy (nothing is
     // freed or re-uploaded on a rate change: hipFree would synchronise the device under the caller's streams)
     struct Taps {
@@ -606,6 +611,7 @@ int bd_destroy(bd_handle h) {
         if (t.uploaded) (void)hipEventDestroy(t.uploaded);
     }
     if (h->d_amax) (void)hipFree(h->d_amax);
+    if (h->d_stack) (void)hipFree(h->d_stack);
     delete h;
     return BD_OK;
 }
@@ -886,10 +892,35 @@ void pointwise(Group& g, int l) {
     g.launch(3 + 2 * l, [&] { bd::launch_pointwise(g.b, g.a, (int64_t)g.gw * L.h_out * L.w_out, L, g.stream); });
 }
 
-// The dense head on the embeddings a tail kernel pooled
+// Floats per window an attached stack's hidden activations take: two rows (ping, pong) of the widest padded layer
+constexpr int kStackRow = (BD_HEAD_MAX_WIDTH + 31) / 32 * 32;
+static_assert(BD_EMBEDDING_SIZE + 2 * kStackRow <= kFloatsB, "pooled embeddings + hidden activations of a stack fit either buffer");
+
+// The attached dense stack (headmlp.hip) on pooled = [gw][1024]: one launch per layer, hidden activations ping-pong through
+// `scratch` (2 * kStackRow floats per window, free at this point of the pass), the last layer lands in the logits - or, in front
+// of a softmax, in scratch too, and the row pass writes the logits (every launch stays idempotent); all in slot 28
+int stack_head(Group& g, const float* pooled, float* scratch) {
+    const std::vector<bd::DenseLayer>& st = g.e->stack;
+    const float* in = pooled;
+    int ld_in = BD_EMBEDDING_SIZE;
+    for (size_t i = 0; i < st.size(); ++i) {
+        const bool last = i + 1 == st.size() && st[i].act != BD_HEAD_SOFTMAX;
+        float* out = last ? g.logits : scratch + (i & 1) * (size_t)g.gw * kStackRow;
+        const int ld_out = last ? st[i].n : (st[i].n + 31) / 32 * 32;
+        g.launch(28, [&] { bd::launch_dense(in, ld_in, g.gw, st[i], out, ld_out, g.stream); });
+        in = out;
+        ld_in = ld_out;
+    }
+    if (st.back().act == BD_HEAD_SOFTMAX)
+        g.launch(28, [&] { bd::launch_softmax_rows(in, ld_in, g.logits, g.gw, st.back().n, g.stream); });
+    return BD_OK;
+}
+
+// The dense head on the embeddings a tail kernel pooled (into the embeddings or b: a is free by now)
 int head(Group& g, const float* pooled) {
-    if (g.logits)
-        g.launch(28, [&] { bd::launch_head(pooled, g.gw, g.e->head_wt, g.e->head_b, g.e->n_classes, g.logits, g.stream); });
+    if (!g.logits) return BD_OK;
+    if (!g.e->stack.empty()) return stack_head(g, pooled, g.a);
+    g.launch(28, [&] { bd::launch_head(pooled, g.gw, g.e->head_wt, g.e->head_b, g.e->n_classes, g.logits, g.stream); });
     return BD_OK;
 }
 
@@ -912,6 +943,12 @@ int walk_layers(Group& g, int from, bool dw_done, int stop_stage) {
         if (stop_stage == 2 * l + 1) return BD_OK;
         pointwise(g, l);
         dw_done = false;
+    }
+    if (stop_stage < 0 && !g.e->stack.empty() && g.logits) {
+        // pool alone (a -> the embeddings, or the front of b: the last 1x1 convolution has read b), then the stack behind it
+        float* const pooled = g.emb ? g.emb : g.b;
+        g.launch(28, [&] { bd::launch_pool_head(g.a, g.gw, nullptr, nullptr, 0, pooled, nullptr, g.stream); });
+        return stack_head(g, pooled, g.b + (size_t)g.gw * BD_EMBEDDING_SIZE);
     }
     if (stop_stage < 0)
         g.launch(28, [&] {
@@ -1439,6 +1476,68 @@ int bd_profile_read(bd_handle h, double* ms, int64_t* launches, int32_t slots) {
         h->launches[i] = 0;
     }
     return BD_PROFILE_SLOTS;
+}
+
+// ---- the dense-stack head (header: buzzdetect_head.h; kernels: headmlp.hip) ----
+int bd_head_abi_version(void) { return BD_HEAD_ABI_VERSION; }
+
+int bd_head_outputs(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_head_outputs: null handle");
+    return h->stack.empty() ? 0 : h->stack.back().n;
+}
+
+int bd_head_attach(bd_handle h, const bd_head_layer* layers, int32_t n_layers) {
+    if (!h || !layers) return fail(BD_EINVAL, "bd_head_attach: null argument");
+    if (h->n_classes != 0 || !h->stack.empty())
+        return fail(BD_EINVAL, "bd_head_attach: the engine already has a head (create it with n_classes == 0)");
+    if (n_layers < 1 || n_layers > BD_HEAD_MAX_LAYERS)
+        return fail(BD_EINVAL, "bd_head_attach: a stack has 1.." + std::to_string(BD_HEAD_MAX_LAYERS) + " layers, not " +
+                                   std::to_string(n_layers));
+    int width = BD_EMBEDDING_SIZE;
+    size_t floats = 0;
+    for (int i = 0; i < n_layers; ++i) {
+        const bd_head_layer& L = layers[i];
+        const std::string who = "bd_head_attach: layer " + std::to_string(i);
+        if (!L.kernel) return fail(BD_EINVAL, who + " has no kernel");
+        if (L.n_out < 1 || L.n_out > BD_HEAD_MAX_WIDTH)
+            return fail(BD_EINVAL, who + ": width " + std::to_string(L.n_out) + " outside 1.." + std::to_string(BD_HEAD_MAX_WIDTH));
+        if (L.n_in != width)
+            return fail(BD_EINVAL, who + " takes " + std::to_string(L.n_in) + " inputs, the layer before it gives " +
+                                       std::to_string(width));
+        if (L.activation < BD_HEAD_LINEAR || L.activation > BD_HEAD_SOFTMAX)
+            return fail(BD_EINVAL, who + ": unknown activation " + std::to_string(L.activation));
+        if (L.activation == BD_HEAD_SOFTMAX && i + 1 != n_layers) return fail(BD_EINVAL, who + ": softmax on a hidden layer");
+        floats += bd::dense_packed_floats(L.n_in, L.n_out) + (size_t)align_up(L.n_out, 4);
+        width = L.n_out;
+    }
+    std::vector<float> host(floats, 0.0f);
+    std::vector<bd::DenseLayer> stack;
+    std::vector<size_t> at;
+    size_t off = 0;
+    for (int i = 0; i < n_layers; ++i) {
+        const bd_head_layer& L = layers[i];
+        at.push_back(off);
+        bd::dense_pack_weights(L.kernel, L.n_in, L.n_out, host.data() + off);
+        off += bd::dense_packed_floats(L.n_in, L.n_out);
+        if (L.bias) std::memcpy(host.data() + off, L.bias, (size_t)L.n_out * sizeof(float));
+        off += (size_t)align_up(L.n_out, 4);
+    }
+    BD_HIP(hipSetDevice(h->device));
+    float* dev = nullptr;
+    BD_HIP(hipMalloc(&dev, floats * sizeof(float)));
+    if (hipMemcpy(dev, host.data(), floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(BD_EHIP, "bd_head_attach: upload failed");
+    }
+    for (int i = 0; i < n_layers; ++i) {
+        const bd_head_layer& L = layers[i];
+        stack.push_back(bd::DenseLayer{L.n_in, L.n_out, L.activation, dev + at[i],
+                                       dev + at[i] + bd::dense_packed_floats(L.n_in, L.n_out)});
+    }
+    h->d_stack = dev;
+    h->stack = std::move(stack);
+    h->n_classes = width;
+    return BD_OK;
 }
 
 // ---- the streamer's way onto the device: pread -> small pinned buffers -> hipMemcpyAsync (header: bd_stager_*) ----

@@ -210,12 +210,17 @@ class HipEngine:
     def __init__(self, embeddername: str = "yamnet_k2", modelname: Optional[str] = "model_general_v3",
                  device: Optional[int] = None, embedder_variables: Optional[str] = None,
                  embedder_blob: Optional[np.ndarray] = None, variables_candidates=None,
-                 synthetic_weights: Optional[bool] = None):
+                 synthetic_weights: Optional[bool] = None, models_dir: Optional[str] = None,
+                 head: Optional["weights.HeadWeights"] = None):
         """``embedder_blob`` / ``embedder_variables``: the weights / an explicit ``variables.data-00000-of-00001``;
         else ``variables_candidates`` (the embedder plugin passes the places beside itself where the reference keeps its
         SavedModel; default: ``embedders/<name>`` under the working directory and under the packaged overlay), then
         ``$BUZZDETECT_YAMNET_VARIABLES``; ``synthetic_weights`` (or ``BUZZDETECT_SYNTHETIC_WEIGHTS=1``) opts in to seeded
-        stand-ins with a warning.  No source: ``FileNotFoundError`` (``weights.load_embedder_blob``)."""
+        stand-ins with a warning.  No source: ``FileNotFoundError`` (``weights.load_embedder_blob``).
+        ``modelname`` / ``models_dir``: the classifier, looked up by ``weights.load_head`` (``models/<modelname>`` under the
+        working directory, ``$BUZZDETECT_MODELS_DIR``, the packaged overlay; ``models_dir`` replaces them); ``head``: an
+        already loaded one.  One linear layer of at most 64 outputs runs fused behind the pool; any other stack is attached
+        with ``bd_head_attach`` and runs one matrix-core launch per layer."""
         self._handle = C.c_void_p()
         self._lib = _lib.load()
         # the weights first (host only): a missing model fails the same way with or without a GPU in the box
@@ -238,17 +243,23 @@ class HipEngine:
         w.mel = mel.ctypes.data_as(C.POINTER(C.c_float))
         self.classes = None
         self.n_classes = 0
-        if modelname is not None:
-            head = weights.load_head(modelname)
+        self.head = None
+        if head is None and modelname is not None:
+            head = weights.load_head(modelname, models_dir)
+        if head is not None:
+            self.head = head
+            self.classes = list(head.classes)
+            self.n_classes = len(self.classes)
+        if head is not None and head.fused:
             hk = np.ascontiguousarray(head.kernel, dtype=np.float32)
             hb = np.ascontiguousarray(head.bias, dtype=np.float32)
             w.head_kernel = hk.ctypes.data_as(C.POINTER(C.c_float))
             w.head_bias = hb.ctypes.data_as(C.POINTER(C.c_float))
             w.n_classes = hb.size
-            self.classes = head.classes
-            self.n_classes = int(hb.size)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.bd_create(C.byref(self._handle), self.device_index, C.byref(w)))
+            if head is not None and not head.fused:
+                self._attach_stack(head.layers)
         # the handle is not thread-safe (include/buzzdetect_hip.h): every call that takes it goes through this lock, so a
         # writer thread that repeats a flagged chunk cannot interleave with the analyzer thread's next predict
         self._lock = threading.RLock()
@@ -260,6 +271,22 @@ class HipEngine:
         self._pinned: list = [None] * 4
         self._pinned_events: list = [None] * 4
         self._pinned_next = 0
+
+    def _attach_stack(self, layers) -> None:
+        """``bd_head_attach``: the Dense stack in place of the fused head (the library copies the arrays)."""
+        arr = (_lib.bd_head_layer * len(layers))()
+        keep = []
+        for i, (kernel, bias, activation) in enumerate(layers):
+            k = np.ascontiguousarray(kernel, dtype=np.float32)
+            b = np.ascontiguousarray(bias, dtype=np.float32)
+            keep += [k, b]
+            arr[i].kernel = k.ctypes.data_as(C.POINTER(C.c_float))
+            arr[i].bias = b.ctypes.data_as(C.POINTER(C.c_float))
+            arr[i].n_in, arr[i].n_out = k.shape
+            arr[i].activation = _lib.HEAD_ACTIVATIONS[activation]
+        _lib.check(self._lib.bd_head_attach(self._handle, arr, len(layers)))
+        if self._lib.bd_head_outputs(self._handle) != self.n_classes:
+            raise RuntimeError("bd_head_attach: the attached stack's width differs from the number of classes")
 
     # ------------------------------------------------------------------ lifecycle
     def close(self) -> None:

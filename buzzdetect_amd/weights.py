@@ -230,18 +230,255 @@ def load_mel(embeddername: str = "yamnet_k2") -> np.ndarray:
     return np.fromfile(os.path.join(DATA_DIR, fn), dtype="<f4").reshape(257, 64).astype(np.float32)
 
 
+HEAD_INPUT = 1024           # the embedding a head starts from
+HEAD_MAX_LAYERS = 8
+HEAD_MAX_WIDTH = 2048
+HEAD_FUSED_MAX = 64         # one linear layer up to this width stays on the head fused behind the pool (BD_MAX_CLASSES)
+MODELS_ENV = "BUZZDETECT_MODELS_DIR"
+PACKAGED_MODEL = "model_general_v3"
+ACTIVATION_OPS = {"Relu": "relu", "Sigmoid": "sigmoid", "Tanh": "tanh", "Softmax": "softmax"}
+_VALUE = "/.ATTRIBUTES/VARIABLE_VALUE"
+
+
+class UnsupportedHeadError(ValueError):
+    """A model directory was found but its classifier is not a stack this engine runs (1..8 Dense layers from the
+    1024-wide embedding, float32, widths 1..2048, linear / ReLU / sigmoid / tanh, softmax last): the message names the
+    op, shape or dtype and the file it was read from."""
+
+
 @dataclass
 class HeadWeights:
-    kernel: np.ndarray  # [1024, n_classes]
-    bias: np.ndarray    # [n_classes]
+    """A classifier head: ``layers`` = [(kernel [in, out], bias [out], activation)], in order from the embedding.
+    ``kernel`` / ``bias`` are those of a head that is one linear layer (``model_general_v3``)."""
+    layers: List[Tuple[np.ndarray, np.ndarray, str]]
     classes: List[str]
+    embeddername: str = "yamnet_k2"
+    digits_results: int = 2
+    metrics_path: Optional[str] = None
+    source: str = ""
+
+    def _single(self) -> Tuple[np.ndarray, np.ndarray, str]:
+        if len(self.layers) != 1 or self.layers[0][2] != "linear":
+            raise AttributeError("kernel / bias exist for a head of one linear layer; this one is a stack (see .layers)")
+        return self.layers[0]
+
+    @property
+    def kernel(self) -> np.ndarray:
+        return self._single()[0]
+
+    @property
+    def bias(self) -> np.ndarray:
+        return self._single()[1]
+
+    @property
+    def fused(self) -> bool:
+        """Does this head run on the kernel fused behind the pool (one linear layer of at most 64 outputs)?"""
+        return len(self.layers) == 1 and self.layers[0][2] == "linear" and self.layers[0][0].shape[1] <= HEAD_FUSED_MAX
 
 
-def load_head(modelname: str = "model_general_v3") -> HeadWeights:
-    """Real dense-head weights (models/model_general_v3/variables, model.py:29)."""
+def dense_chain(nodes, where: str = "saved_model.pb") -> List[Tuple[str, bool, str]]:
+    """The Dense stack of a SavedModel graph, from its decoded nodes (``artifacts.saved_model_nodes``, or a recorded list
+    of them): ``[(activation, has_bias, MatMul node name)]`` in order from the input.
+
+    The serving signature's fully inlined body is the library function ``__inference__wrapped_model_*`` (Keras traces the
+    whole model into it; the other functions call one another); a graph without one is read from the call-free function
+    with the most ``MatMul`` nodes.  From the function's ``Identity`` result the chain is walked back to the input
+    through ``MatMul``, ``BiasAdd``, ``Relu`` / ``Sigmoid`` / ``Tanh`` / ``Softmax`` and ``Identity``; anything else is
+    refused by name, and the walk must end on an argument of the function that no ``ReadVariableOp`` reads (the input, not
+    a variable).  Layers are paired with the bundle by POSITION (``bundle_layer_entries``: the k-th ``MatMul`` from the
+    input takes ``layer_with_weights-k``), which is the order Keras numbers a Sequential's layers in; the resource arguments
+    of the function carry no variable names to check that against."""
+    by_fn: Dict[str, list] = {}
+    for n in nodes:
+        if n.function:
+            by_fn.setdefault(n.function, []).append(n)
+    calls = ("PartitionedCall", "StatefulPartitionedCall")
+    inlined = {f: ns for f, ns in by_fn.items() if any(n.op == "MatMul" for n in ns) and not any(n.op in calls for n in ns)}
+    wrapped = sorted(f for f in inlined if f.startswith("__inference__wrapped_model_"))
+    if wrapped:
+        fn = wrapped[0]
+    elif inlined:
+        fn = max(sorted(inlined), key=lambda f: sum(n.op == "MatMul" for n in inlined[f]))
+    else:
+        raise UnsupportedHeadError(f"{where}: no function with an inlined MatMul chain (not a Dense stack)")
+    body = {n.name: n for n in by_fn[fn]}
+
+    def producer(ref: str):
+        return body.get(ref.split(":", 1)[0])
+
+    def data_inputs(n):
+        return [i for i in n.inputs if not i.startswith("^")]
+
+    outs = [n for n in by_fn[fn] if n.op == "Identity" and n.name == "Identity"]
+    if len(outs) != 1:
+        raise UnsupportedHeadError(f"{where}: function {fn} has {len(outs)} results, a Dense stack has one")
+    node = producer(data_inputs(outs[0])[0])
+    layers: List[Tuple[str, bool, str]] = []       # built from the output backwards
+    act, bias = "linear", False                    # what has been seen since the last MatMul
+    last_ref = data_inputs(outs[0])[0]
+    while node is not None:
+        ins = data_inputs(node)
+        if node.op == "Identity":
+            pass
+        elif node.op in ACTIVATION_OPS:
+            if act != "linear" or bias:
+                raise UnsupportedHeadError(f"{where}: {node.op} node {node.name} does not follow a Dense layer's MatMul / BiasAdd")
+            act = ACTIVATION_OPS[node.op]
+        elif node.op == "BiasAdd":
+            if bias:
+                raise UnsupportedHeadError(f"{where}: two BiasAdd nodes in a row at {node.name}")
+            nxt = producer(ins[0])
+            if nxt is None or nxt.op != "MatMul":
+                raise UnsupportedHeadError(f"{where}: BiasAdd node {node.name} does not follow a MatMul")
+            bias = True
+        elif node.op == "MatMul":
+            for attr in ("transpose_a", "transpose_b"):
+                if node.attrs.get(attr):
+                    raise UnsupportedHeadError(f"{where}: MatMul node {node.name} has {attr}=true")
+            t = node.attrs.get("T")
+            if isinstance(t, dict) and t.get("dtype") not in (None, 1):
+                raise UnsupportedHeadError(f"{where}: MatMul node {node.name} has dtype {t.get('dtype')}, not float32 (1)")
+            w = producer(ins[1]) if len(ins) > 1 else None
+            if w is None or w.op != "ReadVariableOp":
+                raise UnsupportedHeadError(f"{where}: the second operand of MatMul node {node.name} is not a variable")
+            layers.append((act, bias, node.name))
+            act, bias = "linear", False
+        else:
+            raise UnsupportedHeadError(f"{where}: unsupported op {node.op} (node {node.name}) in the classifier; a head is a "
+                                       f"stack of MatMul, BiasAdd, Relu, Sigmoid, Tanh and a final Softmax")
+        last_ref = ins[0] if ins else ""
+        node = producer(ins[0]) if ins else None
+    resources = {i for n in by_fn[fn] if n.op == "ReadVariableOp" for i in n.inputs}
+    if not layers or ":" in last_ref or not last_ref or last_ref in resources:
+        raise UnsupportedHeadError(f"{where}: the chain of function {fn} starts at {last_ref!r}, not at an input argument")
+    if act != "linear" or bias:
+        raise UnsupportedHeadError(f"{where}: an activation or BiasAdd sits on the input, before any MatMul")
+    layers.reverse()
+    if not layers:
+        raise UnsupportedHeadError(f"{where}: function {fn} holds no MatMul between its input and its result")
+    if len(layers) > HEAD_MAX_LAYERS:
+        raise UnsupportedHeadError(f"{where}: {len(layers)} Dense layers, at most {HEAD_MAX_LAYERS} are supported")
+    for k, (a, _, name) in enumerate(layers[:-1]):
+        if a == "softmax":
+            raise UnsupportedHeadError(f"{where}: Softmax on hidden layer {k} ({name}); softmax is supported on the last layer only")
+    return layers
+
+
+def bundle_layer_entries(index: dict, n_layers: int, where: str = "variables.index"):
+    """``[(kernel entry, bias entry or None)]`` of Dense layers 0..n_layers-1: the k-th MatMul of the chain takes
+    ``layer_with_weights-k/kernel`` and ``/bias`` - by NAME, so optimizer slots of the same shapes are never taken.
+    Checks float32, rank, the width limit and that the shapes chain from the 1024-wide embedding."""
+    out = []
+    width = HEAD_INPUT
+    for k in range(n_layers):
+        name = f"layer_with_weights-{k}/kernel"
+        kern = index.get(name + _VALUE) or index.get(name)
+        if kern is None:
+            raise UnsupportedHeadError(f"{where}: the graph has {n_layers} Dense layers but there is no tensor {name}")
+        bias = index.get(f"layer_with_weights-{k}/bias" + _VALUE) or index.get(f"layer_with_weights-{k}/bias")
+        for e in (kern, bias):
+            if e is not None and e.dtype != 1:
+                raise UnsupportedHeadError(f"{where}: {e.name} has dtype {e.dtype}, not float32 (1)")
+        if len(kern.shape) != 2:
+            raise UnsupportedHeadError(f"{where}: {kern.name} has shape {tuple(kern.shape)}, a Dense kernel is [in, out]")
+        if kern.shape[0] != width:
+            raise UnsupportedHeadError(f"{where}: {kern.name} has shape {tuple(kern.shape)} but the layer before it gives "
+                                       f"{width} values (shapes must chain from the {HEAD_INPUT}-wide embedding)")
+        width = int(kern.shape[1])
+        if not 1 <= width <= HEAD_MAX_WIDTH:
+            raise UnsupportedHeadError(f"{where}: {kern.name} has width {width}, outside 1..{HEAD_MAX_WIDTH}")
+        if bias is not None and tuple(bias.shape) != (width,):
+            raise UnsupportedHeadError(f"{where}: {bias.name} has shape {tuple(bias.shape)}, expected ({width},)")
+        out.append((kern, bias))
+    return out
+
+
+def read_model_dir(path: str, modelname: str = "") -> HeadWeights:
+    """A trained model directory in the reference's layout (``config_model.json``, ``saved_model.pb``, ``variables/``,
+    ``tests/metrics.csv``): architecture from the graph, values from the bundle."""
+    from . import artifacts
+    cfg_path = os.path.join(path, "config_model.json")
+    if not os.path.exists(cfg_path):
+        raise FileNotFoundError(f"{cfg_path} not found: a model directory holds config_model.json with its classes")
+    with open(cfg_path) as f:
+        cfg = json.load(f)
+    index_path, data_path = artifacts.bundle_paths(path)
+    index = artifacts.read_bundle_index(index_path)
+    pb = os.path.join(path, "saved_model.pb")
+    nodes = None
+    if os.path.exists(pb):
+        try:
+            nodes = artifacts.saved_model_nodes(pb)
+        except (ValueError, IndexError, UnicodeDecodeError):
+            nodes = None
+    if not nodes:
+        raise UnsupportedHeadError(f"{pb}: no readable graph beside {index_path}; the bundle holds the Dense layers' values "
+                                   f"but not their activations, so the head cannot be built from it alone")
+    chain = dense_chain(nodes, pb)
+    layers = []
+    for (act, has_bias, _), (kern, bias) in zip(chain, bundle_layer_entries(index, len(chain), index_path)):
+        k = artifacts.read_bundle_tensor(data_path, kern).astype(np.float32)
+        if has_bias and bias is None:
+            raise UnsupportedHeadError(f"{index_path}: the graph adds a bias to {kern.name} but the bundle has none")
+        b = (artifacts.read_bundle_tensor(data_path, bias).astype(np.float32) if has_bias
+             else np.zeros(k.shape[1], dtype=np.float32))
+        layers.append((k, b, act))
+    classes = list(cfg["classes"])
+    if len(classes) != layers[-1][0].shape[1]:
+        raise UnsupportedHeadError(f"{cfg_path}: {len(classes)} classes but the last layer of {pb} has width "
+                                   f"{layers[-1][0].shape[1]}")
+    metrics = os.path.join(path, "tests", "metrics.csv")
+    if not os.path.exists(metrics):
+        packaged = os.path.join(DATA_DIR, f"metrics_{modelname}.csv")
+        metrics = packaged if modelname and os.path.exists(packaged) else None
+    return HeadWeights(layers, classes, cfg.get("embeddername", "yamnet_k2"), int(cfg.get("digits_results", 2)), metrics, path)
+
+
+def model_candidates(modelname: str, models_dir: Optional[str] = None) -> List[str]:
+    """Directories ``load_head`` looks at, in order: ``models_dir/<modelname>`` alone when ``models_dir`` is given;
+    else ``models/<modelname>`` under the working directory (the reference's ``cfg.DIR_MODELS``),
+    ``$BUZZDETECT_MODELS_DIR/<modelname>``, the overlay shipped inside this package."""
+    if models_dir is not None:
+        return [os.path.join(models_dir, modelname)]
+    out = [os.path.join(os.getcwd(), "models", modelname)]
+    env = os.environ.get(MODELS_ENV)
+    if env:
+        out.append(os.path.join(env, modelname))
+    out.append(os.path.join(PACKAGED_OVERLAY, "models", modelname))
+    return [c for i, c in enumerate(out) if c not in out[:i]]
+
+
+def _packaged_head(modelname: str) -> HeadWeights:
     with open(os.path.join(DATA_DIR, f"config_{modelname}.json")) as f:
         cfg = json.load(f)
     n = len(cfg["classes"])
     k = np.fromfile(os.path.join(DATA_DIR, f"head_{modelname}_kernel_1024x{n}.f32"), dtype="<f4")
     b = np.fromfile(os.path.join(DATA_DIR, f"head_{modelname}_bias_{n}.f32"), dtype="<f4")
-    return HeadWeights(k.reshape(1024, n).astype(np.float32), b.astype(np.float32), cfg["classes"])
+    metrics = os.path.join(DATA_DIR, f"metrics_{modelname}.csv")
+    for c in model_candidates(modelname):          # a model directory without weights may still carry its own metrics
+        if os.path.exists(os.path.join(c, "tests", "metrics.csv")):
+            metrics = os.path.join(c, "tests", "metrics.csv")
+            break
+    return HeadWeights([(k.reshape(1024, n).astype(np.float32), b.astype(np.float32), "linear")], cfg["classes"],
+                       cfg.get("embeddername", "yamnet_k2"), int(cfg.get("digits_results", 2)),
+                       metrics if os.path.exists(metrics) else None, DATA_DIR)
+
+
+def load_head(modelname: str = PACKAGED_MODEL, models_dir: Optional[str] = None) -> HeadWeights:
+    """The classifier of ``modelname``: the first of ``model_candidates`` that holds a TensorBundle
+    (``variables/variables.index``) is read with ``read_model_dir``; for ``model_general_v3`` alone (and no
+    ``models_dir``) the head packaged with this engine (models/model_general_v3/variables, model.py:29) comes last.
+    Nothing found: ``FileNotFoundError`` naming every place looked at - never a silent fallback."""
+    tried = []
+    for c in model_candidates(modelname, models_dir):
+        if os.path.exists(os.path.join(c, "variables", "variables.index")):
+            _log.info(f"classifier head: {c}")
+            return read_model_dir(c, modelname)
+        tried.append(c + (" (no variables/variables.index)" if os.path.isdir(c) else ""))
+    if modelname == PACKAGED_MODEL and models_dir is None:
+        return _packaged_head(modelname)
+    raise FileNotFoundError(
+        f'model "{modelname}" not found.  Looked for ' + ", ".join(tried) +
+        (f"; ${MODELS_ENV} is not set" if models_dir is None and not os.environ.get(MODELS_ENV) else "") +
+        f".  A model directory holds config_model.json, saved_model.pb and variables/ (tools/modelgen.py writes one); only "
+        f"{PACKAGED_MODEL} is packaged with the engine.")
