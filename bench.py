@@ -14,6 +14,13 @@ count is not a multiple of N is dealt batch by batch; every round of N recording
 inside the timed region).  `python bench.py --gpus N` starts its own N child ranks (torch.distributed.run) when
 it is not already running under one.  Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: set-up, warm-up, the K timed steps, `--dump-outputs`, the line (`value`,
+`ms_per_step`, the workload's description, the board power of the timed region).  Everything else the benchmark measures or
+checks takes runs of its own and sits behind `--full`: the per-kernel HIP-event region with the `roofline` / `stages` objects,
+the exact-f32 loop (`value_strict_f32`, `roofline_strict`), the host-resident, front-end, resampler, analyze() and
+arithmetic-mode legs, and the CPU baseline with its logit comparison.  `--no-kernel-events`, `--no-extras` and
+`--no-cpu-baseline` leave parts of a `--full` run out; `--per-slot` needs `--full`.
+
 `--dump-outputs DIR` (one GPU) also writes the logits the last timed step handed its callers to DIR/logits.npy; the inputs
 are seeded, so two builds run with the same arguments can be compared output for output.
 """
@@ -560,18 +567,23 @@ def analyze_leg(device_index: int, hours: int, chunklength: float, framehop_prop
 
 
 # --------------------------------------------------------------------------------------------------- main
-def main() -> int:
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20, help="timed steps of 50 one-hour recordings each")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything the benchmark measures beside its headline, each in runs of its own after the timed "
+                         "steps: the per-kernel HIP-event region (roofline, stages), the exact-f32 loop, the host-resident, "
+                         "front-end, resampler, analyze() and arithmetic-mode legs, the CPU baseline.  Off by default: a plain "
+                         "run sets up, warms up, times the steps and prints the line")
     ap.add_argument("--cpu-windows", type=int, default=4096,
-                    help="size of the bounded CPU-baseline sample (about 15-25 s of CPU work over 6 passes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket kernels with HIP events")
+                    help="--full: size of the bounded CPU-baseline sample (about 15-25 s of CPU work over 6 passes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full without the region that brackets kernels with HIP events")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the host-resident (H2D-inclusive), analyze() and arithmetic-mode legs")
-    ap.add_argument("--per-slot", action="store_true", help="print per-kernel times to stderr")
+                    help="--full without the exact-f32 loop and the host-resident (H2D-inclusive), analyze() and arithmetic-mode legs")
+    ap.add_argument("--per-slot", action="store_true", help="print per-kernel times to stderr (needs --full: they come from its HIP-event region)")
     ap.add_argument("--streams", type=int, default=2,
                     help="analyzer streams per GPU: batches are dealt round-robin, in issue order, to this many engines, each "
                          "on its own HIP stream (the reference's analyzers_gpu knob, src/analyze.py:218-253).  Two since round 5: "
@@ -591,12 +603,18 @@ def main() -> int:
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the logits the last timed step handed its callers to DIR/*.npy "
                          "(float32 / float64, at most 64 MB: a seeded sample of the recordings beyond that)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dump_outputs is not None and args.gpus != 1:
         ap.error("--dump-outputs needs --gpus 1")
+    if args.per_slot and (not args.full or args.no_kernel_events):
+        ap.error("--per-slot needs --full (and its kernel-event region)")
+    return args
 
+
+def main() -> int:
+    args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return self_launch(args.gpus)
 
@@ -808,9 +826,11 @@ def main() -> int:
         log(f"{value:.0f} windows/s ({1e3 * elapsed / args.steps:.3f} ms/step of {windows_per_step} windows, "
             f"timed region {elapsed:.3f} s)")
 
+    # everything below region 1 is --full's: a plain run goes straight to its line
+
     # region 2 (rank 0's own share, one stream): the same batches with every kernel bracketed by HIP events on
     # its stream (costs a few % of wall time, which is why `value` does not come from this region)
-    events_on = not args.no_kernel_events
+    events_on = args.full and not args.no_kernel_events
     ms = launches = None
     elapsed_events = None
     ev_steps = 10                    # recordings in the event region
@@ -832,7 +852,7 @@ def main() -> int:
     # precision.  The SAME run_files() loop (50 distinct recordings per step as 1024/1024/1024/678-window batches, three
     # analyzer streams, one read-back per step), then the same kernel-event region, in the exact-f32 mode.
     strict = None
-    if world == 1 and not args.no_extras and "f32" in getattr(engine, "POINTWISE_MODES", ()):
+    if args.full and world == 1 and not args.no_extras and "f32" in getattr(engine, "POINTWISE_MODES", ()):
         strict_steps = max(5, min(args.steps, 8))
         for e in engines:
             e.set_pointwise_mode("f32")
@@ -891,8 +911,9 @@ def main() -> int:
                        "sharding": (f"config 4 shape: {args.steps * files_per_step} recordings in total, recording i -> rank i mod {world}, "
                                     f"remainder dealt per batch; one RCCL gather of the [rows,13] logit blocks to rank 0 "
                                     f"per round of {world} recordings, sizes known on the host") if world > 1 else "single GPU",
-                       "timing": "value from K clean steps; per-kernel HIP-event times from a second region "
-                                 f"({ev_steps} recordings, one stream)"},
+                       "timing": "value from K clean steps" + (f"; per-kernel HIP-event times from a second region ({ev_steps} "
+                                                                "recordings, one stream)" if events_on else "")},
+            "full": bool(args.full),
         }
         if args.pointwise_mode is not None:
             out["mode_override"] = args.pointwise_mode
@@ -1029,13 +1050,13 @@ def main() -> int:
                         out["roofline_strict"]["traffic_source"] = PMC_TRAFFIC_STRICT_FILE
                 except (OSError, ValueError, KeyError):
                     pass
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             try:
                 extras(out, args, engines, streams, device, dev_index, hop, step, framehop_s)
             except Exception as exc:                     # an extra leg must never take the headline line down
                 log(f"extras failed: {type(exc).__name__}: {exc}")
                 out["extras_error"] = f"{type(exc).__name__}: {exc}"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(engine, hop, step, args.cpu_windows)
         print(json.dumps(out), flush=True)
 

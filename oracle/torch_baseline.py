@@ -1,6 +1,6 @@
 """torch-CPU restatement of the analyze hot path — TEST INFRASTRUCTURE ONLY.
 
-Two jobs (only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg use it):
+Two jobs (only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py --full``'s ``cpu_baseline`` leg use it):
 
 * an independent second opinion on ``yamnet_oracle`` (different FFT, different conv
   implementation — ``torch.fft`` / ``F.conv2d`` instead of pocketfft / NumPy slicing);

@@ -4,6 +4,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import bench
@@ -110,3 +111,52 @@ def test_the_line_says_what_was_measured():
     assert bench.PEAK_F16_MFMA_TFLOPS == 2500.0 and abs(bench.PEAK_SPLIT_F16_TFLOPS - 2500.0 / 3) < 1e-9
     # pipeline_frac at round 3's driver-observed value: 1.609 M windows/s x 132.12 MFLOP x 3 = 638 TFLOP/s = 0.255
     assert abs(3.0 * bench.POINTWISE_FLOP_PER_WINDOW * 1.609e6 / 1e12 / bench.PEAK_F16_MFMA_TFLOPS - 0.255) < 1e-3
+
+
+def test_full_is_an_option_and_off_by_default(capsys):
+    """A plain run measures the headline alone; what is measured beside it is asked for with --full.  The switches that leave
+    parts of a --full run out are still accepted without it, --per-slot (whose times come from --full's event region) is not."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert plain.full is False and (plain.gpus, plain.steps, plain.warmup, plain.dump_outputs) == (1, 3, 1, None)
+    full = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert full.full is True and not (full.no_cpu_baseline or full.no_extras or full.no_kernel_events)
+    assert bench.parse_args(["--no-cpu-baseline", "--no-extras", "--no-kernel-events"]).full is False
+    assert bench.parse_args(["--full", "--per-slot", "--no-extras"]).per_slot is True
+    for argv in (["--per-slot"], ["--full", "--per-slot", "--no-kernel-events"]):
+        with pytest.raises(SystemExit) as exc:
+            bench.parse_args(argv)
+        assert exc.value.code == 2 and "--per-slot needs --full" in capsys.readouterr().err
+    # every run beside the headline is behind the option (asserted on the source: the runs themselves need a GPU)
+    src = open(bench.__file__).read()
+    for gate in ('events_on = args.full and not args.no_kernel_events', 'if args.full and world == 1 and not args.no_extras and "f32" in',
+                 'if args.full and world == 1 and not args.no_extras:', 'if args.full and world == 1 and not args.no_cpu_baseline:'):
+        assert gate in src, gate
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_and_nothing_measured_beside_it(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` in a process of its own: one JSON line with the headline's keys, `full` false, none
+    of the objects that take runs of their own; --dump-outputs still writes the last step's logits."""
+    import json
+    import subprocess
+    repo = os.path.dirname(os.path.abspath(bench.__file__))
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--files-per-step", "2", "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=300, cwd=repo)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["metric"] == "yamnet_windows_per_s" and out["unit"] == "windows/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32 (split-f16x3 MFMA products, f32 accumulate)" and out["full"] is False
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and (out["steps"], out["warmup"]) == (2, 1)
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 - 2 * 3750) < 1.0            # windows of a step / its seconds
+    assert out["timed_read_back"]["nonfinite"] == 0 and out["timed_read_back"]["batches"] == 2
+    for key in ("cpu_baseline", "roofline", "stages", "strict_f32", "roofline_strict", "value_h2d_s16", "value_h2d_f32",
+                "frontend_roofline", "analyze_audio_s_per_s", "resample_roofline", "config5_1gpu", "value_mode0_f32",
+                "ms_per_recording_with_kernel_events", "extras_error"):
+        assert key not in out, key
+    assert out["value_strict_f32"] is None and out["value_end_to_end_f32_host"] is None
+    logits = np.load(tmp_path / "dump" / "logits.npy")
+    assert logits.shape == (2, 3750, 13) and logits.dtype == np.float32 and np.isfinite(logits).all()
+    assert out["dump_outputs"]["arrays"] == {"logits": [2, 3750, 13], "recording": [2]}

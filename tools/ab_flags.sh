@@ -5,6 +5,6 @@ a=$1; b=$2; pat=${3:-"windows/s"}
 for round in 1 2 3; do
   for arm in A B; do
     flags=$a; [ $arm = B ] && flags=$b
-    timeout -k 10 300 python bench.py --steps 10 --warmup 3 --per-slot --no-cpu-baseline --no-extras $flags 2>&1 >/dev/null | grep -E "$pat|windows/s \(" | sed "s/^/[$arm:$flags r$round] /"
+    timeout -k 10 300 python bench.py --steps 10 --warmup 3 --full --per-slot --no-cpu-baseline --no-extras $flags 2>&1 >/dev/null | grep -E "$pat|windows/s \(" | sed "s/^/[$arm:$flags r$round] /"
   done
 done

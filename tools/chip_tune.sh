@@ -11,7 +11,7 @@ done > gpurun_out/r05/tune_trace_$tag.log
 cat gpurun_out/r05/tune_trace_$tag.log
 for round in 1 2; do
   for t in $tunes; do
-    BD_CHIP_TUNE=$t timeout -k 10 300 python bench.py --steps 10 --warmup 3 --per-slot --no-cpu-baseline --no-extras 2>&1 >/dev/null | grep -E "sep8|windows/s" | sed "s/^/[tune $t r$round] /"
+    BD_CHIP_TUNE=$t timeout -k 10 300 python bench.py --steps 10 --warmup 3 --full --per-slot --no-cpu-baseline --no-extras 2>&1 >/dev/null | grep -E "sep8|windows/s" | sed "s/^/[tune $t r$round] /"
   done
 done > gpurun_out/r05/tune_bench_$tag.log
 cat gpurun_out/r05/tune_bench_$tag.log
