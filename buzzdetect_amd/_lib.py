@@ -179,6 +179,19 @@ HEAD_PROTOTYPES = {
     "bd_head_outputs": (C.c_int, [C.c_void_p]),
 }
 
+ANYRATE_ABI_VERSION = 1
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_anyrate.h
+ANYRATE_PROTOTYPES = {
+    "bd_anyrate_abi_version": (C.c_int, []),
+    "bd_anyrate_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "bd_resample_any": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_void_p]),
+    "bd_resample_any_s16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_void_p]),
+    "bd_resample_any_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -211,7 +224,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             raise RuntimeError(f"{path} is older than its sources and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
-            + list(HEAD_PROTOTYPES.items()):
+            + list(HEAD_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -223,6 +236,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: PCM ABI version {lib.bd_pcm_abi_version()} != {PCM_ABI_VERSION}; rebuild")
     if lib.bd_head_abi_version() != HEAD_ABI_VERSION:
         raise RuntimeError(f"{path}: head ABI version {lib.bd_head_abi_version()} != {HEAD_ABI_VERSION}; rebuild")
+    if lib.bd_anyrate_abi_version() != ANYRATE_ABI_VERSION:
+        raise RuntimeError(f"{path}: any-ratio ABI version {lib.bd_anyrate_abi_version()} != {ANYRATE_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

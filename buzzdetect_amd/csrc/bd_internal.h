@@ -127,6 +127,21 @@ bool fir_plan_build(int up, int down, const double* taps, int half, FirPlanHost*
 void launch_fir_mfma(const void* in, bool s16, int64_t n_in, int channels, const FirPlan& plan, float* out, int64_t n_out,
                      hipStream_t stream);
 
+// The any-ratio resampler (anyrate.hip, include/buzzdetect_anyrate.h): geometry of one rate ratio.  The table is
+// [rows][kw] float32: row r holds g(q - W - phase_r), q = 0 .. 2 W, zero-padded to kw.
+struct AnyratePlan {
+    int up, down;
+    int exact;                 // 1: rows = up, the polyphase rows themselves; 0: rows = 259, phases -1 .. 257 of 256
+    int rows, W, kw;           // kw = round_up(2 W + 1, 64)
+    int tj, kp, spread;        // outputs per tile, taps per staged piece (multiple of 64), inputs a tile's outputs start over
+    long long step_n;          // floor(j down / up) and (j down) mod up advance by these per 4 outputs (one wave's stride)
+    int step_r;
+};
+bool anyrate_plan(int up, int down, AnyratePlan* plan);            // false: outside the accepted range
+void anyrate_table(const AnyratePlan& plan, std::vector<float>* table);
+void launch_anyrate(const void* in, bool s16, int64_t n_in, int channels, const AnyratePlan& plan, const float* table,
+                    float* out, int64_t n_out, hipStream_t stream);
+
 // ---- launchers (each enqueues exactly one kernel on `stream`) ----
 void launch_logmel(const float* pcm, int64_t n_valid, int64_t n_frames, float* logmel,
                    const FeTables* tables, hipStream_t stream);

@@ -13,6 +13,7 @@
 
 #include "bd_internal.h"
 
+#include "../../include/buzzdetect_anyrate.h"
 #include "../../include/buzzdetect_head.h"
 
 namespace {
@@ -95,6 +96,16 @@ struct bd_engine {
         hipEvent_t uploaded;
     };
     std::vector<Taps> taps;
+    // the coefficient rows of the ratios those plans do not cover (anyrate.hip), under the same rules
+    struct AnyTaps {
+        bd::AnyratePlan plan;
+        int quality;
+        float* dev;
+        std::vector<float> host;
+        hipStream_t upload_stream;
+        hipEvent_t uploaded;
+    };
+    std::vector<AnyTaps> any_taps;
     int resample_quality = BD_RESAMPLE_HQ;
     // profiling
     bool profiling = false;
@@ -610,6 +621,10 @@ int bd_destroy(bd_handle h) {
         (void)hipFree(t.dev);
         if (t.uploaded) (void)hipEventDestroy(t.uploaded);
     }
+    for (auto& t : h->any_taps) {
+        (void)hipFree(t.dev);
+        if (t.uploaded) (void)hipEventDestroy(t.uploaded);
+    }
     if (h->d_amax) (void)hipFree(h->d_amax);
     if (h->d_stack) (void)hipFree(h->d_stack);
     delete h;
@@ -800,6 +815,69 @@ int bd_resample(bd_handle h, const float* in_dev, int64_t n_in, int32_t channels
 int bd_resample_s16(bd_handle h, const int16_t* in_dev, int64_t n_in, int32_t channels, int32_t rate_in,
                     int32_t rate_out, float* out_dev, void* stream) {
     return resample_any(h, in_dev, true, n_in, channels, rate_in, rate_out, out_dev, stream);
+}
+
+// include/buzzdetect_anyrate.h: bd_resample's own route where it has one (resample_any above, untouched), anyrate_kernel elsewhere
+static int resample_every(bd_handle h, const void* in_dev, bool s16, int64_t n_in, int32_t channels, int32_t rate_in,
+                          int32_t rate_out, float* out_dev, void* stream) {
+    if (!h || !out_dev || (!in_dev && n_in > 0)) return fail(BD_EINVAL, "bd_resample_any: null argument");
+    if (n_in < 0 || channels <= 0 || rate_in <= 0 || rate_out <= 0) return fail(BD_EINVAL, "bd_resample_any: bad size");
+    if (misaligned(in_dev) || misaligned(out_dev)) return fail(BD_EINVAL, "bd_resample_any: pointers need 16-byte alignment");
+    int up, down;
+    rational_ratio(rate_in, rate_out, &up, &down);
+    const int quality = h->resample_quality;
+    if (up == 1 && down == 1) return resample_any(h, in_dev, s16, n_in, channels, rate_in, rate_out, out_dev, stream);
+    for (const auto& t : h->taps)                           // a ratio bd_resample has run before is one it accepts
+        if (t.up == up && t.down == down && t.quality == quality)
+            return resample_any(h, in_dev, s16, n_in, channels, rate_in, rate_out, out_dev, stream);
+    const bd_engine::AnyTaps* filt = nullptr;
+    for (const auto& t : h->any_taps)
+        if (t.plan.up == up && t.plan.down == down && t.quality == quality) filt = &t;
+    if (!filt && bd_resample_supported(rate_in, rate_out, quality) == 1)
+        return resample_any(h, in_dev, s16, n_in, channels, rate_in, rate_out, out_dev, stream);
+    BD_HIP(hipSetDevice(h->device));
+    if (!filt) {                                            // first use of this ratio: design, upload in stream order
+        bd_engine::AnyTaps t;
+        if (quality != BD_RESAMPLE_HQ)
+            return fail(BD_EINVAL, "bd_resample_any: the scipy-quality filter has no any-ratio form and bd_resample refuses this rate pair");
+        if (!bd::anyrate_plan(up, down, &t.plan))
+            return fail(BD_EINVAL, "bd_resample_any: rate pair outside the any-ratio range (rates below 2^27, coefficient table "
+                                   "within BD_ANYRATE_MAX_TABLE_BYTES)");
+        if (h->any_taps.size() >= 64) return fail(BD_EINVAL, "bd_resample_any: more than 64 distinct any-ratio rate pairs on one engine");
+        if (h->any_taps.capacity() < 64) h->any_taps.reserve(64);      // entries never move: uploads read from them
+        t.quality = quality;
+        bd::anyrate_table(t.plan, &t.host);
+        t.dev = nullptr;
+        t.upload_stream = (hipStream_t)stream;
+        t.uploaded = nullptr;
+        BD_HIP(hipMalloc(&t.dev, t.host.size() * sizeof(float)));
+        if (hipEventCreateWithFlags(&t.uploaded, hipEventDisableTiming) != hipSuccess) {
+            (void)hipFree(t.dev);
+            return fail(BD_EHIP, "bd_resample_any: hipEventCreate failed");
+        }
+        h->any_taps.push_back(std::move(t));
+        filt = &h->any_taps.back();
+        BD_HIP(hipMemcpyAsync(filt->dev, filt->host.data(), filt->host.size() * sizeof(float), hipMemcpyHostToDevice,
+                              (hipStream_t)stream));
+        BD_HIP(hipEventRecord(filt->uploaded, (hipStream_t)stream));
+    } else if (filt->upload_stream != (hipStream_t)stream) {
+        BD_HIP(hipStreamWaitEvent((hipStream_t)stream, filt->uploaded, 0));
+    }
+    const int64_t n_out = (n_in * up + down - 1) / down;
+    if ((n_out + filt->plan.tj - 1) / filt->plan.tj > 0x7fffffffll) return fail(BD_ERANGE, "bd_resample_any: more than 2^31 tiles; split the chunk");
+    bd::launch_anyrate(in_dev, s16, n_in, channels, filt->plan, filt->dev, out_dev, n_out, (hipStream_t)stream);
+    BD_HIP(hipGetLastError());
+    return BD_OK;
+}
+
+int bd_resample_any(bd_handle h, const float* in_dev, int64_t n_in, int32_t channels, int32_t rate_in, int32_t rate_out,
+                    float* out_dev, void* stream) {
+    return resample_every(h, in_dev, false, n_in, channels, rate_in, rate_out, out_dev, stream);
+}
+
+int bd_resample_any_s16(bd_handle h, const int16_t* in_dev, int64_t n_in, int32_t channels, int32_t rate_in,
+                        int32_t rate_out, float* out_dev, void* stream) {
+    return resample_every(h, in_dev, true, n_in, channels, rate_in, rate_out, out_dev, stream);
 }
 
 int bd_patches(bd_handle h, const float* logmel_dev, int64_t n_frames, int32_t patch_step, float* patches_dev,

@@ -385,7 +385,7 @@ class Pipeline:
             return self._skip("planner", job, f"{exc}; skipping", logging.WARNING,
                               f"unreadable, skipped: {job.shortpath} ({exc})")
         if track.samplerate != 16000 and not self._rate_supported(track.samplerate):
-            track.close()                                   # (the reference resamples any rate; bd_resample refuses these)
+            track.close()                                   # (outside bd_resample_any's range, buzzdetect_anyrate.h)
             return self._skip("planner", job, f"{job.shortpath}: cannot resample {track.samplerate} Hz to 16000 Hz on the device; skipping",
                               logging.WARNING, f"sample rate {track.samplerate} Hz not supported, skipped: {job.shortpath}")
         job.fresh = not os.path.exists(job.rf.path_partial)
@@ -403,10 +403,10 @@ class Pipeline:
             self._put(self.q_units, ReadUnit(job, (float(chunk[0]), float(chunk[1]))))
 
     def _rate_supported(self, rate: int) -> bool:
-        """bd_resample_supported for the quality the engines run (host only: no handle, no device)."""
+        """bd_anyrate_supported for the quality the engines run (host only: no handle, no device)."""
         if rate not in self._rates:
             from . import _lib
-            self._rates[rate] = _lib.load().bd_resample_supported(int(rate), 16000, int(self.resample_quality)) == 1
+            self._rates[rate] = _lib.load().bd_anyrate_supported(int(rate), 16000, int(self.resample_quality)) == 1
         return self._rates[rate]
 
     def _planner(self) -> None:

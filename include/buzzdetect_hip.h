@@ -147,7 +147,8 @@ BD_API int bd_debug_fir_plan(int32_t rate_in, int32_t rate_out, int32_t* geometr
 /* Host only: 1 when bd_resample / bd_resample_s16 accept rate_in -> rate_out at `quality` (BD_RESAMPLE_*), 0 when they refuse
    it with BD_EINVAL - the ratio does not reduce to <= 4096, or its low-pass is longer than the span the vector kernel
    stages per tile and the matrix-core form does not fit either (HQ: down / up > ~43, e.g. 768 kHz -> 16 kHz).  The
-   reference resamples any rate (librosa.resample, src/stream/worker.py:128); such a file has to be decimated in two steps. */
+   reference resamples any rate (librosa.resample, src/stream/worker.py:128); bd_resample_any (buzzdetect_anyrate.h) takes
+   these pairs too, and bd_anyrate_supported is the query for it. */
 BD_API int bd_resample_supported(int32_t rate_in, int32_t rate_out, int32_t quality);
 BD_API int bd_resample(bd_handle h, const float* in_dev, int64_t n_in, int32_t channels, int32_t rate_in,
                        int32_t rate_out, float* out_dev, void* stream);
