@@ -482,35 +482,18 @@ class HipEngine:
         """Samples [start, start + frames) of a FLAC file (default: to its end) decoded on the device: float32
         [frames, channels], as soundfile.read(dtype="float32") gives them.  A frame that fails its checks ends the audio
         early (the tensor is shorter), as a file cut short does."""
-        from .flacio import FlacDecoder, FlacTrack
-        track = FlacTrack(path)
-        try:
-            start = min(max(int(start), 0), track.frames)
-            n = track.frames - start if frames is None else min(int(frames), track.frames - start)
-            out = torch.empty((max(n, 0), track.channels), dtype=torch.int16 if track.is_s16 else torch.float32, device=self.device)
-            if n <= 0:
-                return out.to(torch.float32)
-            off, end = track.byte_range(start, n)
-            stream = self._stream()
-            dec = FlacDecoder(torch, self.device)
-            comp = dec.staging(end - off)
-            data = np.frombuffer(os.pread(track.fd, end - off, off), np.uint8)
-            comp[: data.size].copy_(torch.from_numpy(data.copy()), non_blocking=False)
-            with torch.cuda.device(self.device):
-                dec.decode(track, data.size, start, n, out.data_ptr(), stream)
-            stream.synchronize()
-            got = int(dec.result().samples)
-        finally:
-            track.close()
-        out = out[:got]
-        return out.to(torch.float32) / 32768.0 if track.is_s16 else out
+        from .flacio import FlacTrack
+        return self._read_decoded(FlacTrack(path), start, frames)
 
     def read_pcm(self, path: str, start: int = 0, frames: Optional[int] = None) -> torch.Tensor:
         """Frames [start, start + frames) of an AIFF / AU / Wave64 / G.711- or ADPCM-coded WAVE file (pcmio.py; default: to
         its end) decoded on the device: float32 [frames, channels], as soundfile.read(dtype="float32") gives them.  An
         invalid ADPCM block header ends the audio early (the tensor is shorter), as a file cut short does."""
-        from .pcmio import PcmDecoder, PcmTrack
-        track = PcmTrack(path)
+        from .pcmio import PcmTrack
+        return self._read_decoded(PcmTrack(path), start, frames)
+
+    def _read_decoded(self, track, start: int, frames: Optional[int]) -> torch.Tensor:
+        """read_flac / read_pcm: the range staged and decoded piece by piece by the track's device decoder; closes the track."""
         try:
             start = min(max(int(start), 0), track.frames)
             n = track.frames - start if frames is None else min(int(frames), track.frames - start)
@@ -518,10 +501,10 @@ class HipEngine:
             if n <= 0:
                 return out.to(torch.float32)
             stream = self._stream()
-            dec = PcmDecoder(torch, self.device)
+            dec = track.decoder(torch, self.device)
             bpf = out.element_size() * track.channels
             got = 0
-            for p, m in track.pieces(start, n):            # pieces of whole blocks below pcmio.PIECE_BYTES
+            for p, m in track.pieces(start, n):            # (pcmio: pieces of whole blocks below pcmio.PIECE_BYTES)
                 off, end = track.byte_range(p, m)
                 comp = dec.staging(end - off)
                 data = np.frombuffer(os.pread(track.fd, end - off, off), np.uint8)

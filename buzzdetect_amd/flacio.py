@@ -16,6 +16,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
+from .devdecode import DeviceDecoder
 from .wavio import WavFormatError, WavTrack
 
 SEARCH_WINDOW = 64 << 10          # bytes read per probe of the locator
@@ -38,7 +39,14 @@ def open_track(path: str):
     return WavTrack(path)
 
 
+class FlacDecoder(DeviceDecoder):
+    """One thread's device-side FLAC decoder state (bd_flac_decode)."""
+    status_type, workspace_fn, decode_fn = _lib.bd_flac_status, "bd_flac_workspace_bytes", "bd_flac_decode"
+
+
 class FlacTrack:
+    decoder = FlacDecoder             # the device decoder of this track's ranges
+
     def __init__(self, path: str):
         self.path = path
         self._lib = _lib.load()
@@ -224,14 +232,28 @@ class FlacTrack:
         """Bytes of one decoded frame: int16 for 16-bit streams, float32 otherwise."""
         return self.channels * (2 if self.is_s16 else 4)
 
-    def decode_host(self, first: int, n: int) -> Tuple[np.ndarray, "_lib.bd_flac_status"]:
-        """Samples [first, first + n) decoded on the host: ([got, channels] int16 or float32, status)."""
+    @property
+    def header(self) -> "_lib.bd_flac_streaminfo":
+        """What the decode calls take as the stream's description."""
+        return self.si
+
+    def pieces(self, first: int, n: int) -> List[Tuple[int, int]]:
+        """A FLAC range is staged and decoded as one piece (pcmio.PcmTrack.pieces)."""
+        return [(first, n)]
+
+    def decode_host_into(self, first: int, n: int, out_ptr: Optional[int]) -> "_lib.bd_flac_status":
+        """Samples [first, first + n) decoded on the host to `out_ptr` (int16 or float32, interleaved); the status."""
         a, b = self.byte_range(first, n)
         data = np.frombuffer(self._pread(a, b - a), np.uint8)
-        out = np.zeros((max(n, 0), self.channels), np.int16 if self.is_s16 else np.float32)
         st = _lib.bd_flac_status()
         _lib.check(self._lib.bd_flac_decode_host(data.ctypes.data if data.size else None, data.size, C.byref(self.si), first, n,
-                                                 out.ctypes.data if out.size else None, C.byref(st)))
+                                                 out_ptr, C.byref(st)))
+        return st
+
+    def decode_host(self, first: int, n: int) -> Tuple[np.ndarray, "_lib.bd_flac_status"]:
+        """Samples [first, first + n) decoded on the host: ([got, channels] int16 or float32, status)."""
+        out = np.zeros((max(n, 0), self.channels), np.int16 if self.is_s16 else np.float32)
+        st = self.decode_host_into(first, n, out.ctypes.data if out.size else None)
         return out[: st.samples], st
 
     def __del__(self):
@@ -242,37 +264,3 @@ class FlacTrack:
         if fd is not None:
             os.close(fd)
 
-
-class FlacDecoder:
-    """One thread's device-side decoder state: the compressed bytes of a range, the workspace and the status record,
-    all grown on demand and reused (the caller synchronises its stream before the next use)."""
-
-    def __init__(self, torch, device):
-        self._torch, self._device = torch, device
-        self._lib = _lib.load()
-        self.comp = None
-        self.ws = None
-        self.status = torch.zeros(C.sizeof(_lib.bd_flac_status), dtype=torch.uint8, device=device)
-        self.status_host = torch.zeros(C.sizeof(_lib.bd_flac_status), dtype=torch.uint8).pin_memory()
-
-    def _grow(self, buf, nbytes: int):
-        if buf is None or buf.numel() < nbytes:
-            buf = self._torch.empty(max(int(nbytes * 1.25), 1 << 20), dtype=self._torch.uint8, device=self._device)
-        return buf
-
-    def staging(self, nbytes: int):
-        """The device buffer a range of `nbytes` compressed bytes goes to (rounded up to 4 bytes, as bd_flac_decode reads)."""
-        self.comp = self._grow(self.comp, (nbytes + 3) // 4 * 4 + 8)
-        return self.comp
-
-    def decode(self, track: FlacTrack, nbytes: int, first: int, n: int, out_ptr: int, stream) -> None:
-        """Enqueue the decode of the staged range on `stream`; `result` reads the status once the stream is synchronised."""
-        need = _lib.check(self._lib.bd_flac_workspace_bytes(C.byref(track.si), nbytes, n))
-        self.ws = self._grow(self.ws, need)
-        _lib.check(self._lib.bd_flac_decode(self.comp.data_ptr(), nbytes, C.byref(track.si), first, n, out_ptr, self.ws.data_ptr(),
-                                            self.ws.numel(), self.status.data_ptr(), stream.cuda_stream))
-        with self._torch.cuda.stream(stream):
-            self.status_host.copy_(self.status, non_blocking=True)
-
-    def result(self) -> "_lib.bd_flac_status":
-        return _lib.bd_flac_status.from_buffer_copy(self.status_host.numpy().tobytes())

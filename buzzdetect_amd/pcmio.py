@@ -29,6 +29,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
+from .devdecode import DeviceDecoder
 from .wavio import FORMAT_EXTENSIBLE, FORMAT_FLOAT, FORMAT_PCM, WavFormatError
 
 FORMAT_MS_ADPCM, FORMAT_ALAW, FORMAT_ULAW, FORMAT_IMA_ADPCM = 2, 6, 7, 0x11
@@ -189,7 +190,14 @@ def _extended_rate(b: bytes) -> Fraction:
     return -v if se & 0x8000 else v
 
 
+class PcmDecoder(DeviceDecoder):
+    """One thread's device-side decoder state for pcmio's formats (bd_pcm_decode); its workspace is kept zeroed."""
+    status_type, workspace_fn, decode_fn, ws_zeroed = _lib.bd_pcm_status, "bd_pcm_workspace_bytes", "bd_pcm_decode", 256
+
+
 class PcmTrack:
+    decoder = PcmDecoder              # the device decoder of this track's ranges
+
     def __init__(self, path: str):
         self.path = path
         self._fd = os.open(path, os.O_RDONLY)
@@ -378,14 +386,24 @@ class PcmTrack:
             at = stop
         return out
 
-    def decode_host(self, first: int, n: int) -> Tuple[np.ndarray, "_lib.bd_pcm_status"]:
-        """Frames [first, first + n) decoded on the host: ([got, channels] int16 or float32, status)."""
+    @property
+    def header(self) -> "_lib.bd_pcm_format":
+        """What the decode calls take as the stream's description."""
+        return self.fmt
+
+    def decode_host_into(self, first: int, n: int, out_ptr: Optional[int]) -> "_lib.bd_pcm_status":
+        """Frames [first, first + n) decoded on the host to `out_ptr` (int16 or float32, interleaved); the status."""
         a, b = self.byte_range(first, n)
         data = np.frombuffer(self._pread(a, b - a), np.uint8)
-        out = np.zeros((max(n, 0), self.channels), np.int16 if self.is_s16 else np.float32)
         st = _lib.bd_pcm_status()
         _lib.check(_lib.load().bd_pcm_decode_host(data.ctypes.data if data.size else None, data.size, C.byref(self.fmt), first,
-                                                  max(n, 0), out.ctypes.data if out.size else None, C.byref(st)))
+                                                  max(n, 0), out_ptr, C.byref(st)))
+        return st
+
+    def decode_host(self, first: int, n: int) -> Tuple[np.ndarray, "_lib.bd_pcm_status"]:
+        """Frames [first, first + n) decoded on the host: ([got, channels] int16 or float32, status)."""
+        out = np.zeros((max(n, 0), self.channels), np.int16 if self.is_s16 else np.float32)
+        st = self.decode_host_into(first, n, out.ctypes.data if out.size else None)
         return out[: st.samples], st
 
     def __del__(self):
@@ -396,35 +414,3 @@ class PcmTrack:
         if fd is not None:
             os.close(fd)
 
-
-class PcmDecoder:
-    """One thread's device-side decoder state: the staged bytes of a range, the workspace and the status record, grown on
-    demand and reused (the caller synchronises its stream before the next use)."""
-
-    def __init__(self, torch, device):
-        self._torch, self._device = torch, device
-        self._lib = _lib.load()
-        self.comp = None
-        self.ws = torch.zeros(256, dtype=torch.uint8, device=device)
-        self.status = torch.zeros(C.sizeof(_lib.bd_pcm_status), dtype=torch.uint8, device=device)
-        self.status_host = torch.zeros(C.sizeof(_lib.bd_pcm_status), dtype=torch.uint8).pin_memory()
-
-    def staging(self, nbytes: int):
-        """The device buffer a range of `nbytes` goes to (rounded up to 4 bytes, as bd_pcm_decode reads)."""
-        need = (nbytes + 3) // 4 * 4 + 8
-        if self.comp is None or self.comp.numel() < need:
-            self.comp = self._torch.empty(max(int(need * 1.25), 1 << 20), dtype=self._torch.uint8, device=self._device)
-        return self.comp
-
-    def decode(self, track: PcmTrack, nbytes: int, first: int, n: int, out_ptr: int, stream) -> None:
-        """Enqueue the decode of the staged range on `stream`; `result` reads the status once the stream is synchronised."""
-        need = _lib.check(self._lib.bd_pcm_workspace_bytes(C.byref(track.fmt), nbytes, n))
-        if self.ws.numel() < need:
-            self.ws = self._torch.zeros(need, dtype=self._torch.uint8, device=self._device)
-        _lib.check(self._lib.bd_pcm_decode(self.comp.data_ptr(), nbytes, C.byref(track.fmt), first, n, out_ptr, self.ws.data_ptr(),
-                                           self.ws.numel(), self.status.data_ptr(), stream.cuda_stream))
-        with self._torch.cuda.stream(stream):
-            self.status_host.copy_(self.status, non_blocking=True)
-
-    def result(self) -> "_lib.bd_pcm_status":
-        return _lib.bd_pcm_status.from_buffer_copy(self.status_host.numpy().tobytes())

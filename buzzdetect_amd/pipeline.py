@@ -12,6 +12,10 @@ that consumes ~45 MB/s of 16-bit PCM per 10 k windows/s is not left waiting:
                 device buffers) when it enters the bounded queue (depth 2 x readers, coordination.py:84-102).  Only
                 readers x 16 MB of host memory is ever page-locked, whatever the chunk length (round 6: the ring of
                 chunk-sized pinned slots of round 5 page-locked ~1 GB inside the first call).  Reads release the GIL.
+                Every format takes ONE path (`_read_unit`: slot, stage, fill, short-read rule, event, ChunkTask); only the
+                fill differs, chosen by what the track offers: WAV (`_fill_wav`, above), little-endian 16-bit pcmio
+                (`_fill_raw`: as 16-bit WAV), FLAC and coded pcmio (`_fill_decoded`: the file's bytes to a device buffer
+                of the reader, decoded there into the slot by the decoder the track names).
     analyzers   `analyzers` threads per GPU (the reference's analyzers_gpu; docs/source/tuning.rst:111), each
                 constructing and initialising ITS OWN engine in-thread (src/inference/worker.py:21,78) on its own
                 HIP stream: wait for the chunk's copy event, device-side downmix / resample / s16 -> f32, up to 64
@@ -43,8 +47,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import framing, results
-from .flacio import FlacDecoder, FlacTrack, open_track
-from .pcmio import PcmDecoder, PcmTrack
+from .flacio import open_track
 from .wavio import WavFormatError, WavTrack
 
 PROGRESS = logging.INFO - 5
@@ -457,58 +460,23 @@ class Pipeline:
         if have <= 0:                                       # the whole chunk lies behind the end of a file cut short
             self._bad_read(job, track, track.frames)
             return self._drop(job)
-        if isinstance(track, FlacTrack):
-            return self._read_flac_unit(unit, a, want, have)
-        if isinstance(track, PcmTrack):
-            return self._read_pcm_unit(unit, a, want, have)
-        bpf = track.bytes_per_frame
-        out_bpf = bpf if track.is_s16 else track.channels * 4          # any other sample format: float32 on the host
+        out_bpf = track.out_bytes_per_frame                 # the slot holds 16-bit PCM as int16, anything else as float32
         slot, dev = self.pool.acquire(have * out_bpf, self.aborted)
         try:
             t0 = time.perf_counter()
-            if self.device is None:                        # host-only stage (tests): straight into the pool's host buffer
-                host = dev.numpy()
-                got = track.read_raw_into(a, have, host)
-                at = got * bpf
-                if got and not track.is_s16:
-                    f32 = track.convert(host[:at].copy())
-                    at = f32.size * 4
-                    host[:at] = f32.reshape(-1).view(np.uint8)
-                st = None
+            st = None                                      # host-only stage (tests): the slot is the pool's host buffer
+            if self.device is not None:
+                st, t0 = self._reader_stage(t0)
+            if not hasattr(track, "pieces"):               # by what the track offers: WavTrack has neither
+                fill = self._fill_wav
+            elif st is not None and getattr(track, "raw_s16", False):
+                fill = self._fill_raw
             else:
-                st = getattr(self._stage, "st", None)
-                if st is None:
-                    st = self._stage.st = ReaderStage.take(self.torch, self.device)
-                    with self.lock:
-                        self._stages.append(st)
-                    self._busy("pin", st.pin_seconds)
-                    t0 = time.perf_counter()
-                if track.is_s16:                           # the file's bytes as they lie: one native call, no interpreter lock
-                    fd, off, nb = track.file_range(a, have)
-                    at = st.read(fd, off, nb, dev)
-                    got = at // bpf
-                else:                                      # converted to float32 on the host, piece by piece
-                    piece = max(1, STAGE_BYTES // max(bpf, out_bpf))
-                    got = at = 0
-                    while got < have:
-                        n = min(piece, have - got)
-                        box = {}
-
-                        def fill(buf, n=n, first=a + got):
-                            r = box["frames"] = track.read_raw_into(first, n, buf)
-                            if r == 0:
-                                return 0
-                            f32 = track.convert(buf[: r * bpf].copy())
-                            buf[: f32.size * 4] = f32.reshape(-1).view(np.uint8)
-                            return f32.size * 4
-                        at += st.send(fill, dev.data_ptr() + at)
-                        got += box["frames"]
-                        if box["frames"] < n:
-                            break
-            self._busy("read", time.perf_counter() - t0)
-            if got < want:                                 # short read (src/stream/worker.py:119-127): say it, truncate the
-                self._bad_read(job, track, a + got)        # chunk, and the file ends here
-                chunk = (chunk[0], round(chunk[0] + got / track.samplerate, 1))
+                fill = self._fill_decoded
+            got = fill(track, a, have, dev, st, t0)
+            if got < want:                                 # short read (src/stream/worker.py:119-127), a FLAC frame that fails,
+                self._bad_read(job, track, a + got)        # an invalid block header: say it, truncate the chunk, and the
+                chunk = (chunk[0], round(chunk[0] + got / track.samplerate, 1))      # file ends here
             if got == 0:
                 self.pool.release(slot)
                 return self._drop(job)
@@ -519,143 +487,98 @@ class Pipeline:
             with self.lock:
                 self.report.chunks += 1
                 self.report.audio_seconds += float(chunk[1] - chunk[0])
-            self._put(self.q_analyze, ChunkTask(job, chunk, slot, at, got, track.channels, track.samplerate, track.is_s16, ready))
+            self._put(self.q_analyze, ChunkTask(job, chunk, slot, got * out_bpf, got, track.channels, track.samplerate,
+                                                track.is_s16, ready))
         except BaseException:
             self.pool.release(slot)
             raise
 
-    def _read_flac_unit(self, unit: ReadUnit, a: int, want: int, have: int) -> None:
-        """A FLAC chunk: its compressed bytes to a device buffer of this reader, decoded there into the pool slot (int16 for
-        16-bit streams, float32 otherwise: what a WAV chunk of the same samples becomes), then the same ChunkTask."""
-        from . import _lib
-        import ctypes
-        job, chunk, track = unit.job, unit.chunk, unit.job.track
-        slot, dev = self.pool.acquire(have * track.out_bytes_per_frame, self.aborted)
-        try:
+    def _reader_stage(self, t0: float) -> Tuple[ReaderStage, float]:
+        """This thread's stage, taken on first use: page-locking its buffers is `pin` time, and the clock restarts behind it."""
+        st = getattr(self._stage, "st", None)
+        if st is None:
+            st = self._stage.st = ReaderStage.take(self.torch, self.device)
+            self._stage.decoders = {}                      # this thread's device decoders, by the class a track names
+            with self.lock:
+                self._stages.append(st)
+            self._busy("pin", st.pin_seconds)
             t0 = time.perf_counter()
-            off, end = track.byte_range(a, have)
-            st = None
-            if self.device is None:                        # host-only stage (tests): the host decoder
-                data = np.frombuffer(os.pread(track.fd, end - off, off), np.uint8)
-                status = _lib.bd_flac_status()
-                host = dev.numpy()
-                _lib.check(_lib.load().bd_flac_decode_host(data.ctypes.data if data.size else None, data.size, ctypes.byref(track.si),
-                                                           a, have, host.ctypes.data, ctypes.byref(status)))
-                self._busy("read", time.perf_counter() - t0)
+        return st, t0
+
+    # The fills: `have` frames from frame `a` on into the slot `dev`, in the slot's layout; each returns the frames it got and
+    # accounts its own time (`st` None: the host-only stage, where everything is `read`).
+    def _fill_wav(self, track, a: int, have: int, dev, st, t0: float) -> int:
+        bpf = track.bytes_per_frame
+        if st is None:
+            host = dev.numpy()
+            got = track.read_raw_into(a, have, host)
+            if got and not track.is_s16:
+                f32 = track.convert(host[: got * bpf].copy())
+                host[: f32.size * 4] = f32.reshape(-1).view(np.uint8)
+        elif track.is_s16:                                 # the file's bytes as they lie: one native call, no interpreter lock
+            fd, off, nb = track.file_range(a, have)
+            got = st.read(fd, off, nb, dev) // bpf
+        else:                                              # converted to float32 on the host, piece by piece
+            piece = max(1, STAGE_BYTES // max(bpf, track.out_bytes_per_frame))
+            got = at = 0
+            while got < have:
+                n = min(piece, have - got)
+                box = {}
+
+                def fill(buf, n=n, first=a + got):
+                    r = box["frames"] = track.read_raw_into(first, n, buf)
+                    if r == 0:
+                        return 0
+                    f32 = track.convert(buf[: r * bpf].copy())
+                    buf[: f32.size * 4] = f32.reshape(-1).view(np.uint8)
+                    return f32.size * 4
+                at += st.send(fill, dev.data_ptr() + at)
+                got += box["frames"]
+                if box["frames"] < n:
+                    break
+        self._busy("read", time.perf_counter() - t0)
+        return got
+
+    def _fill_raw(self, track, a: int, have: int, dev, st, t0: float) -> int:
+        """Little-endian 16-bit samples of a pcmio track are the slot's bytes already and go straight into it, as a 16-bit
+        WAV chunk does."""
+        off, end = track.byte_range(a, have)
+        got = min(st.read(track.fd, off, end - off, dev) // track.out_bytes_per_frame, have)
+        self._busy("read", time.perf_counter() - t0)
+        return got
+
+    def _fill_decoded(self, track, a: int, have: int, dev, st, t0: float) -> int:
+        """A FLAC or pcmio chunk, piece by piece (one piece unless the range reaches pcmio.PIECE_BYTES): the piece's bytes as
+        they lie in the file to a device buffer of this reader (`read`), decoded there into its place in the slot (`decode`:
+        enqueue, wait, status).  Host-only: the track's host decoder over the same pieces.  A piece that comes back short
+        ends the audio."""
+        bpf = track.out_bytes_per_frame
+        if st is None:
+            host = dev.numpy()
+        else:
+            dec = self._stage.decoders.get(track.decoder)
+            if dec is None:
+                dec = self._stage.decoders[track.decoder] = track.decoder(self.torch, self.device)
+        got = 0
+        for p, m in track.pieces(a, have):
+            if st is None:
+                k = int(track.decode_host_into(p, m, host[(p - a) * bpf:].ctypes.data).samples)
             else:
-                st = getattr(self._stage, "st", None)
-                if st is None:
-                    st = self._stage.st = ReaderStage.take(self.torch, self.device)
-                    with self.lock:
-                        self._stages.append(st)
-                    self._busy("pin", st.pin_seconds)
-                    t0 = time.perf_counter()
-                dec = getattr(self._stage, "flac", None)
-                if dec is None:
-                    dec = self._stage.flac = FlacDecoder(self.torch, self.device)
-                comp = dec.staging(end - off)
-                nbytes = st.read(track.fd, off, end - off, comp)
+                off, end = track.byte_range(p, m)
+                nbytes = st.read(track.fd, off, end - off, dec.staging(end - off))
                 t1 = time.perf_counter()
                 self._busy("read", t1 - t0)
-                dec.decode(track, nbytes, a, have, dev.data_ptr(), st.stream)
+                dec.decode(track, nbytes, p, m, dev.data_ptr() + (p - a) * bpf, st.stream)
                 st.stream.synchronize()                    # (a reader may block; the analyzers never wait for this)
-                status = dec.result()
-                self._busy("decode", time.perf_counter() - t1)
-            got = int(status.samples)
-            at = got * track.out_bytes_per_frame
-            if got < want:                                 # a frame that fails (or a file cut short) ends the readable audio
-                self._bad_read(job, track, a + got)
-                chunk = (chunk[0], round(chunk[0] + got / track.samplerate, 1))
-            if got == 0:
-                self.pool.release(slot)
-                return self._drop(job)
-            ready = None
-            if st is not None:
-                ready = self.events.take()
-                ready.record(st.stream)
-            with self.lock:
-                self.report.chunks += 1
-                self.report.audio_seconds += float(chunk[1] - chunk[0])
-            self._put(self.q_analyze, ChunkTask(job, chunk, slot, at, got, track.channels, track.samplerate, track.is_s16, ready))
-        except BaseException:
-            self.pool.release(slot)
-            raise
-
-    def _read_pcm_unit(self, unit: ReadUnit, a: int, want: int, have: int) -> None:
-        """An AIFF / AU / Wave64 / coded-WAVE chunk (pcmio.PcmTrack): its bytes as they lie in the file to a device buffer of
-        this reader, decoded there into the pool slot (int16 for 16-bit linear, G.711 and ADPCM, float32 otherwise: what a
-        WAV chunk of the same samples becomes), then the same ChunkTask.  Little-endian 16-bit samples are the slot's
-        bytes already and go straight into it, as a 16-bit WAV chunk does."""
-        from . import _lib
-        import ctypes
-        job, chunk, track = unit.job, unit.chunk, unit.job.track
-        slot, dev = self.pool.acquire(have * track.out_bytes_per_frame, self.aborted)
-        try:
-            t0 = time.perf_counter()
-            bpf = track.out_bytes_per_frame
-            st = None
-            got = 0
-            if self.device is None:                        # host-only stage (tests): the host decoder
-                host = dev.numpy()
-                for p, m in track.pieces(a, have):         # (the same pieces as the device path)
-                    off, end = track.byte_range(p, m)
-                    data = np.frombuffer(os.pread(track.fd, end - off, off), np.uint8)
-                    status = _lib.bd_pcm_status()
-                    _lib.check(_lib.load().bd_pcm_decode_host(data.ctypes.data if data.size else None, data.size,
-                                                              ctypes.byref(track.fmt), p, m, host[(p - a) * bpf:].ctypes.data,
-                                                              ctypes.byref(status)))
-                    got += int(status.samples)
-                    if status.samples < m:
-                        break
-                self._busy("read", time.perf_counter() - t0)
-            else:
-                st = getattr(self._stage, "st", None)
-                if st is None:
-                    st = self._stage.st = ReaderStage.take(self.torch, self.device)
-                    with self.lock:
-                        self._stages.append(st)
-                    self._busy("pin", st.pin_seconds)
-                    t0 = time.perf_counter()
-                if track.raw_s16:
-                    off, end = track.byte_range(a, have)
-                    got = min(st.read(track.fd, off, end - off, dev) // bpf, have)
-                    self._busy("read", time.perf_counter() - t0)
-                else:
-                    dec = getattr(self._stage, "pcm", None)
-                    if dec is None:
-                        dec = self._stage.pcm = PcmDecoder(self.torch, self.device)
-                    for p, m in track.pieces(a, have):     # one piece unless the range reaches PIECE_BYTES
-                        off, end = track.byte_range(p, m)
-                        comp = dec.staging(end - off)
-                        nbytes = st.read(track.fd, off, end - off, comp)
-                        t1 = time.perf_counter()
-                        self._busy("read", t1 - t0)
-                        dec.decode(track, nbytes, p, m, dev.data_ptr() + (p - a) * bpf, st.stream)
-                        st.stream.synchronize()            # (a reader may block; the analyzers never wait for this)
-                        k = int(dec.result().samples)
-                        t0 = time.perf_counter()
-                        self._busy("decode", t0 - t1)
-                        got += k
-                        if k < m:
-                            break
-            at = got * track.out_bytes_per_frame
-            if got < want:                                 # an invalid block header (or a file cut short) ends the audio
-                self._bad_read(job, track, a + got)
-                chunk = (chunk[0], round(chunk[0] + got / track.samplerate, 1))
-            if got == 0:
-                self.pool.release(slot)
-                return self._drop(job)
-            ready = None
-            if st is not None:
-                ready = self.events.take()
-                ready.record(st.stream)
-            with self.lock:
-                self.report.chunks += 1
-                self.report.audio_seconds += float(chunk[1] - chunk[0])
-            self._put(self.q_analyze, ChunkTask(job, chunk, slot, at, got, track.channels, track.samplerate, track.is_s16, ready))
-        except BaseException:
-            self.pool.release(slot)
-            raise
+                k = int(dec.result().samples)
+                t0 = time.perf_counter()
+                self._busy("decode", t0 - t1)
+            got += k
+            if k < m:
+                break
+        if st is None:
+            self._busy("read", time.perf_counter() - t0)
+        return got
 
     def _reader(self, rid: int) -> None:
         try:

@@ -122,6 +122,11 @@ class WavTrack:
     def bytes_per_frame(self) -> int:
         return self._block
 
+    @property
+    def out_bytes_per_frame(self) -> int:
+        """Bytes of one frame in a chunk's slot: 16-bit PCM as it lies in the file, anything else float32."""
+        return self._block if self.is_s16 else self.channels * 4
+
     def file_range(self, frame: int, n: int):
         """(file descriptor, byte offset, byte count) of ``n`` frames from ``frame`` on, clipped to what the file holds:
         for readers that do their own positioned reads (bd_stager_read)."""
