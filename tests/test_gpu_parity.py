@@ -116,6 +116,7 @@ def test_frontend_matches_golden_rows(engine):
 
 # --------------------------------------------------------------------------- CNN stages
 def test_every_cnn_stage_against_oracle(engine_mode, weights_bundle):
+    """Per channel, on weights that leave no channel dead: tests/test_cnn_channels_gpu.py."""
     engine = engine_mode
     b = weights_bundle
     x = O.synthetic_audio(HOP * 3 + 500, seed=11)
