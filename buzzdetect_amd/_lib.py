@@ -192,6 +192,37 @@ ANYRATE_PROTOTYPES = {
     "bd_resample_any_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
+TRAIN_ABI_VERSION = 1
+TRAIN_SLICE_ROWS = 256
+TRAIN_FUSED_MAX_WIDTH = 64
+TRAIN_MAX_BATCH = 65536
+TRAIN_LOSSES = {"categorical": 0, "binary": 1}
+TRAIN_OPTIMIZERS = {"sgd": 0, "adam": 1}
+
+
+class bd_train_optimizer(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("learning_rate", C.c_float), ("beta_1", C.c_float), ("beta_2", C.c_float),
+                ("epsilon", C.c_float), ("reserved", C.c_int32)]
+
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_train.h
+TRAIN_PROTOTYPES = {
+    "bd_train_abi_version": (C.c_int, []),
+    "bd_trainer_create": (C.c_int, [C.c_int, C.POINTER(bd_head_layer), C.c_int32, C.c_int32, C.POINTER(bd_train_optimizer),
+                                    C.c_int32, C.POINTER(C.c_void_p)]),
+    "bd_trainer_destroy": (C.c_int, [C.c_void_p]),
+    "bd_trainer_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_trainer_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_trainer_gradients": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_trainer_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_trainer_logits": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_trainer_mean_loss": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_float)]),
+    "bd_trainer_set_fusion": (C.c_int, [C.c_void_p, C.c_int32]),
+    "bd_trainer_workspace_floats": (C.c_int64, [C.c_void_p]),
+    "bd_trainer_workspace_fill": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "bd_trainer_workspace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -224,7 +255,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             raise RuntimeError(f"{path} is older than its sources and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
-            + list(HEAD_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()):
+            + list(HEAD_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -238,6 +269,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: head ABI version {lib.bd_head_abi_version()} != {HEAD_ABI_VERSION}; rebuild")
     if lib.bd_anyrate_abi_version() != ANYRATE_ABI_VERSION:
         raise RuntimeError(f"{path}: any-ratio ABI version {lib.bd_anyrate_abi_version()} != {ANYRATE_ABI_VERSION}; rebuild")
+    if lib.bd_train_abi_version() != TRAIN_ABI_VERSION:
+        raise RuntimeError(f"{path}: trainer ABI version {lib.bd_train_abi_version()} != {TRAIN_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

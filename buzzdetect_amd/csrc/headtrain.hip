@@ -1,0 +1,688 @@
+// The classifier-head trainer (include/buzzdetect_train.h): forward, loss, backward and update of a Dense stack on
+// embeddings, in exact float32 on v_mfma_f32_32x32x2_f32.
+//
+// Every product is one routine, mma_chain: a wave owns a 32 x 32 output tile and walks the reduced index alone in ascending
+// super-steps of 8, in headmlp.hip's operand map (lane l supplies A[i = l & 31][k] and B[k][j = l & 31], lane-half h takes
+// k = 8 s + 4 h + j for the j-th instruction of super-step s), four super-steps in flight ahead of the sixteen instructions
+// that use them.  What differs between the three products is where a lane finds its operands:
+//   forward  Y = act(A W + b)      reduce over n_in    A: 16 bytes of a row (row rows[r] of X for layer 0)   B: W[k][col]
+//   dA       G' = (G W^T) * act'   reduce over n_out   A: 16 bytes of a row of G                             B: W[col][k]
+//   dW       P_s = A^T G           reduce over the rows of slice s   A: A[row][col]                          B: G[row][col]
+// Elements outside a matrix are zeros chosen by a compare, never loaded; no address outside a row that exists is formed.
+// The parameters stay row-major [n_in][n_out] + [n_out] (the update writes them every step; no fragment copy to keep in step).
+//
+// Order of sums (the determinism contract): an output element is one chain of fused multiply-adds in ascending k.  dW reduces
+// over the batch: slice s is rows [256 s, 256 s + 256) - kSliceRows, a constant - its partial goes to workspace
+// [slice][n_in n_out + n_out], and apply_kernel adds the partials in ascending s before the optimizer's update.  Row losses go
+// to a buffer and one workgroup adds them in a fixed tree.  Nothing depends on the grid or the number of compute units.
+//
+// fused_step_kernel (one layer, n_out <= 64): a workgroup of eight waves owns a slice and calls the same three routines -
+// logits of its 256 rows, their deltas, the slice's dW partial - so the partial's second walk over the slice's rows of X finds
+// them in the cache the first walk filled: X comes from HBM once per step.
+#include "bd_internal.h"
+
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <string>
+
+#include "../../include/buzzdetect_train.h"
+
+namespace bd {
+
+void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
+
+namespace {
+
+constexpr int kSliceRows = BD_TRAIN_SLICE_ROWS;
+static_assert(kSliceRows % 32 == 0, "a slice is whole 32-row steps of the matrix instruction");
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ float act_fwd(float x, int act) {       // headmlp.hip's head_act
+    if (act == BD_HEAD_RELU) return fmaxf(x, 0.0f);
+    if (act == BD_HEAD_SIGMOID) return 1.0f / (1.0f + expf(-x));
+    if (act == BD_HEAD_TANH) return tanhf(x);
+    return x;
+}
+
+__device__ __forceinline__ float act_grad(float y, int act) {      // from the stored activation y
+    if (act == BD_HEAD_RELU) return y > 0.0f ? 1.0f : 0.0f;
+    if (act == BD_HEAD_SIGMOID) return y * (1.0f - y);
+    if (act == BD_HEAD_TANH) return 1.0f - y * y;
+    return 1.0f;
+}
+
+// acc[32][32] = sum over super-steps s < n_super (a multiple of 4) of fa(s) x fb(s): fa(s) / fb(s) give this lane's four
+// operand elements k = 8 s + 4 (lane >> 5) + 0..3
+template <class FA, class FB>
+__device__ __forceinline__ v16f mma_chain(int n_super, FA fa, FB fb) {
+    float4 a[4], b[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        a[q] = fa(q);
+        b[q] = fb(q);
+    }
+    v16f acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    for (int s = 0; s < n_super; s += 4) {
+        float4 an[4], bn[4];
+        const bool more = s + 4 < n_super;
+        if (more) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                an[q] = fa(s + 4 + q);
+                bn[q] = fb(s + 4 + q);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].x, b[q].x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].y, b[q].y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].z, b[q].z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].w, b[q].w, acc, 0, 0, 0);
+        }
+        if (more) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                a[q] = an[q];
+                b[q] = bn[q];
+            }
+        }
+    }
+    return acc;
+}
+
+// accumulator r of lane l is element [(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31] of the tile
+__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// Y[32 tr ..][32 tc ..] = act(A W + b).  A is [.][lda] with lda >= round_up(K, 32) (X: ldx >= 1024 = K), rows < B; `rows`
+// (layer 0 only) names the row of A that batch row r reads.  P = W [K][N] then b [N].
+__device__ __forceinline__ void forward_tile(const float* __restrict__ A, int64_t lda, const int* __restrict__ rows, int B, int K,
+                                             const float* __restrict__ P, int N, int act, float* Y, int ldy, int tr,
+                                             int tc, int lane) {
+    const int half = lane >> 5, li = lane & 31;
+    const int br = min(32 * tr + li, B - 1);
+    const int64_t src = rows ? rows[br] : br;
+    const float* ap = A + src * lda + 4 * half;
+    const int col = 32 * tc + li;
+    const bool col_ok = col < N;
+    const float* wp = P + (col_ok ? col : 0);
+    const v16f acc = mma_chain((K + 31) / 32 * 4,
+        [&](int s) {
+            float4 v = *reinterpret_cast<const float4*>(ap + 8 * s);
+            const int k0 = 8 * s + 4 * half;
+            v.x = k0 + 0 < K ? v.x : 0.0f;
+            v.y = k0 + 1 < K ? v.y : 0.0f;
+            v.z = k0 + 2 < K ? v.z : 0.0f;
+            v.w = k0 + 3 < K ? v.w : 0.0f;
+            return v;
+        },
+        [&](int s) {
+            const int k0 = 8 * s + 4 * half;
+            float4 v;
+            v.x = col_ok && k0 + 0 < K ? wp[(size_t)(k0 + 0) * N] : 0.0f;
+            v.y = col_ok && k0 + 1 < K ? wp[(size_t)(k0 + 1) * N] : 0.0f;
+            v.z = col_ok && k0 + 2 < K ? wp[(size_t)(k0 + 2) * N] : 0.0f;
+            v.w = col_ok && k0 + 3 < K ? wp[(size_t)(k0 + 3) * N] : 0.0f;
+            return v;
+        });
+    if (!col_ok) return;
+    const float bv = P[(size_t)K * N + col];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = 32 * tr + acc_row(r, half);
+        if (row < B) Y[(size_t)row * ldy + col] = act_fwd(acc[r] + bv, act);
+    }
+}
+
+// Gp[32 tr ..][32 tc ..] = (G W^T) * act'(Yp): G [B][ldg] (columns < N), W [K][N], Yp / Gp [B][ldp] (columns < K)
+__device__ __forceinline__ void input_grad_tile(const float* __restrict__ G, int ldg, int B, int K, const float* __restrict__ W,
+                                                int N, const float* __restrict__ Yp, int act_p, float* __restrict__ Gp, int ldp,
+                                                int tr, int tc, int lane) {
+    const int half = lane >> 5, li = lane & 31;
+    const float* gp = G + (size_t)min(32 * tr + li, B - 1) * ldg + 4 * half;
+    const int col = 32 * tc + li;                        // an input of the layer: a row of W
+    const bool col_ok = col < K;
+    const float* wp = W + (size_t)(col_ok ? col : 0) * N;
+    const v16f acc = mma_chain((N + 31) / 32 * 4,
+        [&](int s) {
+            float4 v = *reinterpret_cast<const float4*>(gp + 8 * s);
+            const int n0 = 8 * s + 4 * half;
+            v.x = n0 + 0 < N ? v.x : 0.0f;
+            v.y = n0 + 1 < N ? v.y : 0.0f;
+            v.z = n0 + 2 < N ? v.z : 0.0f;
+            v.w = n0 + 3 < N ? v.w : 0.0f;
+            return v;
+        },
+        [&](int s) {
+            const int n0 = 8 * s + 4 * half;
+            float4 v;
+            v.x = col_ok && n0 + 0 < N ? wp[n0 + 0] : 0.0f;
+            v.y = col_ok && n0 + 1 < N ? wp[n0 + 1] : 0.0f;
+            v.z = col_ok && n0 + 2 < N ? wp[n0 + 2] : 0.0f;
+            v.w = col_ok && n0 + 3 < N ? wp[n0 + 3] : 0.0f;
+            return v;
+        });
+    if (!col_ok) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = 32 * tr + acc_row(r, half);
+        if (row < B) {
+            const size_t at = (size_t)row * ldp + col;
+            Gp[at] = acc[r] * act_grad(Yp[at], act_p);
+        }
+    }
+}
+
+// part[32 tk ..][32 tn ..] = sum over batch rows r0 <= r < r1 of A[r][.]^T G[r][.]: part is the slice's [K][N]
+__device__ __forceinline__ void weight_grad_tile(const float* __restrict__ A, int64_t lda, const int* __restrict__ rows, int r0,
+                                                 int r1, int K, const float* G, int ldg, int N,
+                                                 float* __restrict__ part, int tk, int tn, int lane) {
+    const int half = lane >> 5, li = lane & 31;
+    const int kk = 32 * tk + li, col = 32 * tn + li;
+    const bool kk_ok = kk < K, col_ok = col < N;
+    const v16f acc = mma_chain((r1 - r0 + 31) / 32 * 4,
+        [&](int s) {
+            const int r = r0 + 8 * s + 4 * half;
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[j] = 0.0f;
+                if (kk_ok && r + j < r1) {
+                    const int64_t src = rows ? rows[r + j] : r + j;
+                    v[j] = A[src * lda + kk];
+                }
+            }
+            return make_float4(v[0], v[1], v[2], v[3]);
+        },
+        [&](int s) {
+            const int r = r0 + 8 * s + 4 * half;
+            float4 v;
+            v.x = col_ok && r + 0 < r1 ? G[(size_t)(r + 0) * ldg + col] : 0.0f;
+            v.y = col_ok && r + 1 < r1 ? G[(size_t)(r + 1) * ldg + col] : 0.0f;
+            v.z = col_ok && r + 2 < r1 ? G[(size_t)(r + 2) * ldg + col] : 0.0f;
+            v.w = col_ok && r + 3 < r1 ? G[(size_t)(r + 3) * ldg + col] : 0.0f;
+            return v;
+        });
+    if (!col_ok) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = 32 * tk + acc_row(r, half);
+        if (row < K) part[(size_t)row * N + col] = acc[r];
+    }
+}
+
+// the slice's db partial for columns 32 tn ..: lane-half h adds rows r0 + h, r0 + h + 2, ... in ascending order, then h = 0 + h = 1
+__device__ __forceinline__ void bias_grad_tile(const float* G, int ldg, int r0, int r1, int N, float* __restrict__ part_b,
+                                               int tn, int lane) {
+    const int half = lane >> 5, col = 32 * tn + (lane & 31);
+    float sum = 0.0f;
+    if (col < N)
+        for (int r = r0 + half; r < r1; r += 2) sum += G[(size_t)r * ldg + col];
+    const float other = __shfl_xor(sum, 32, 64);
+    if (half == 0 && col < N) part_b[col] = sum + other;
+}
+
+// One row of the last layer: its loss and the delta of its logits.  One wave; lane l takes columns l, l + 64, ... in ascending
+// order and the 64 partial results meet in a butterfly, the same order for every row wherever it sits.
+__device__ __forceinline__ void loss_row(const float* z, float* g, int C, int loss,
+                                         const void* __restrict__ targets, int row, float inv, float* __restrict__ row_loss,
+                                         int lane) {
+    if (loss == BD_TRAIN_CATEGORICAL) {
+        const int label = reinterpret_cast<const int*>(targets)[row];
+        float m = -INFINITY;
+        for (int c = lane; c < C; c += 64) m = fmaxf(m, z[c]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        float sum = 0.0f;
+        for (int c = lane; c < C; c += 64) sum += expf(z[c] - m);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        for (int c = lane; c < C; c += 64) g[c] = (expf(z[c] - m) / sum - (c == label ? 1.0f : 0.0f)) * inv;
+        if (lane == 0) row_loss[row] = (m + logf(sum)) - z[min(max(label, 0), C - 1)];
+    } else {
+        const float* t = reinterpret_cast<const float*>(targets) + (size_t)row * C;
+        float sum = 0.0f;
+        for (int c = lane; c < C; c += 64) {
+            const float x = z[c], y = t[c];
+            const float e = expf(-fabsf(x));
+            sum += (fmaxf(x, 0.0f) - x * y) + log1pf(e);
+            const float sig = x >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+            g[c] = (sig - y) * inv;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        if (lane == 0) row_loss[row] = sum;
+    }
+}
+
+// ---- kernels ----
+
+__global__ __launch_bounds__(256) void forward_kernel(const float* __restrict__ A, int64_t lda, const int* __restrict__ rows, int B,
+                                                       int K, const float* __restrict__ P, int N, int act, float* __restrict__ Y,
+                                                       int ldy) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tr = 2 * blockIdx.x + (wave & 1), tc = 2 * blockIdx.y + (wave >> 1);
+    if (32 * tr >= B || 32 * tc >= N) return;           // (no barrier in this kernel)
+    forward_tile(A, lda, rows, B, K, P, N, act, Y, ldy, tr, tc, lane);
+}
+
+__global__ __launch_bounds__(256) void input_grad_kernel(const float* __restrict__ G, int ldg, int B, int K,
+                                                          const float* __restrict__ W, int N, const float* __restrict__ Yp, int act_p,
+                                                          float* __restrict__ Gp, int ldp) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tr = 2 * blockIdx.x + (wave & 1), tc = 2 * blockIdx.y + (wave >> 1);
+    if (32 * tr >= B || 32 * tc >= K) return;
+    input_grad_tile(G, ldg, B, K, W, N, Yp, act_p, Gp, ldp, tr, tc, lane);
+}
+
+// grid (ceil(tiles / 4), slices): a wave per 32 x 32 tile of a slice's partial; the waves of the first row of tiles add db
+__global__ __launch_bounds__(256) void weight_grad_kernel(const float* __restrict__ A, int64_t lda, const int* __restrict__ rows,
+                                                           int B, int K, const float* __restrict__ G, int ldg, int N,
+                                                           float* __restrict__ ws) {
+    const int lane = threadIdx.x & 63;
+    const int tiles_n = (N + 31) / 32, tiles = (K + 31) / 32 * tiles_n;
+    const int t = 4 * blockIdx.x + (threadIdx.x >> 6);
+    if (t >= tiles) return;
+    const int slice = blockIdx.y, r0 = slice * kSliceRows, r1 = min(B, r0 + kSliceRows);
+    float* part = ws + (size_t)slice * ((size_t)K * N + N);
+    const int tk = t / tiles_n, tn = t % tiles_n;
+    weight_grad_tile(A, lda, rows, r0, r1, K, G, ldg, N, part, tk, tn, lane);
+    if (tk == 0) bias_grad_tile(G, ldg, r0, r1, N, part + (size_t)K * N, tn, lane);
+}
+
+__global__ __launch_bounds__(256) void loss_rows_kernel(const float* __restrict__ Z, float* __restrict__ G, int ld, int B, int C,
+                                                         int loss, const void* __restrict__ targets, float inv,
+                                                         float* __restrict__ row_loss) {
+    const int row = 4 * blockIdx.x + (threadIdx.x >> 6);
+    if (row >= B) return;
+    loss_row(Z + (size_t)row * ld, G + (size_t)row * ld, C, loss, targets, row, inv, row_loss, threadIdx.x & 63);
+}
+
+// One layer of at most 64 outputs; grid = slices, eight waves.  Z / G [B][64].
+__global__ __launch_bounds__(512) void fused_step_kernel(const float* __restrict__ X, int64_t ldx, const int* __restrict__ rows,
+                                                           int B, int K, const float* __restrict__ P, int N, float* Z,
+                                                           float* G, int ld, int loss,
+                                                           const void* __restrict__ targets, float inv, float* __restrict__ row_loss,
+                                                           float* __restrict__ ws) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slice = blockIdx.x, r0 = slice * kSliceRows, r1 = min(B, r0 + kSliceRows);
+    const int tiles_n = (N + 31) / 32;
+    for (int t = wave; t < 8 * tiles_n; t += 8) {
+        const int tr = r0 / 32 + (t & 7), tc = t >> 3;
+        if (32 * tr < r1) forward_tile(X, ldx, rows, B, K, P, N, BD_HEAD_LINEAR, Z, ld, tr, tc, lane);
+    }
+    __syncthreads();                                     // the slice's logits, written above by this workgroup
+    for (int row = r0 + wave; row < r1; row += 8)
+        loss_row(Z + (size_t)row * ld, G + (size_t)row * ld, N, loss, targets, row, inv, row_loss, lane);
+    __syncthreads();                                     // the slice's deltas
+    float* part = ws + (size_t)slice * ((size_t)K * N + N);
+    const int tiles = (K + 31) / 32 * tiles_n;
+    for (int t = wave; t < tiles; t += 8) {
+        const int tk = t / tiles_n, tn = t % tiles_n;
+        weight_grad_tile(X, ldx, rows, r0, r1, K, G, ld, N, part, tk, tn, lane);
+        if (tk == 0) bias_grad_tile(G, ld, r0, r1, N, part + (size_t)K * N, tn, lane);
+    }
+}
+
+// One workgroup: thread t adds rows t, t + 256, ... in ascending order (in double: the sum is not what limits the loss), then a
+// fixed tree.  out[0] = the batch's mean loss; acc[0] += mean * B, acc[1] += B (the running sum of bd_trainer_mean_loss).
+__global__ __launch_bounds__(256) void loss_sum_kernel(const float* __restrict__ row_loss, int B, double scale, float* __restrict__ out,
+                                                        double* __restrict__ acc) {
+    __shared__ double part[256];
+    double sum = 0.0;
+    for (int r = threadIdx.x; r < B; r += 256) sum += (double)row_loss[r];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double mean = part[0] * scale;
+        if (out) out[0] = (float)mean;
+        if (acc) {
+            acc[0] += mean * B;
+            acc[1] += B;
+        }
+    }
+}
+
+struct Update {
+    int kind;
+    float lr, b1, b2, eps;
+    float lr_t;                     // Adam: lr sqrt(1 - b2^t) / (1 - b1^t) of this step
+};
+
+// element i of a layer's [W | b]: the slices' partials in ascending order, then the optimizer
+__global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ ws, int slices, int n, float* __restrict__ grad,
+                                                     float* __restrict__ P, float* __restrict__ m, float* __restrict__ v, Update u) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float g = ws[i];
+    for (int s = 1; s < slices; ++s) g += ws[(size_t)s * n + i];
+    grad[i] = g;
+    if (u.kind == BD_TRAIN_ADAM) {
+        const float mi = u.b1 * m[i] + (1.0f - u.b1) * g;
+        const float vi = u.b2 * v[i] + (1.0f - u.b2) * (g * g);
+        m[i] = mi;
+        v[i] = vi;
+        P[i] = P[i] - u.lr_t * mi / (sqrtf(vi) + u.eps);
+    } else {
+        P[i] = P[i] - u.lr * g;
+    }
+}
+
+__global__ void fill_kernel(uint32_t* p, size_t n, uint32_t pattern) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = pattern;
+}
+
+int fail(int code, const std::string& msg) {
+    set_error(msg);
+    return code;
+}
+
+#define BDT_HIP(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return fail(BD_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+struct Layer {
+    int k, n, act, ld;              // ld = round_up(n, 32): row stride of y and g
+    float *p, *grad, *m, *v;        // [k n + n] each: W then b (m, v: Adam only)
+    float *y, *g;                   // [max_batch][ld]: activations (the last layer's: logits) and d loss / d pre-activation
+};
+
+}  // namespace
+}  // namespace bd
+
+struct bd_trainer_s {
+    int device = 0, n_layers = 0, loss = 0, max_batch = 0;
+    bd_train_optimizer opt{};
+    int64_t step = 0;
+    bool fused = true;
+    bd::Layer layers[BD_HEAD_MAX_LAYERS]{};
+    float* pool = nullptr;          // one allocation behind every pointer above and below
+    float* ws = nullptr;            // [slices][k n + n] of the layer at work
+    int64_t ws_floats = 0;
+    float* row_loss = nullptr;      // [max_batch]
+    double* acc = nullptr;          // running loss sum, rows
+    hipStream_t last = nullptr;
+};
+
+namespace bd {
+namespace {
+
+bool fusable(const bd_trainer_s* t) { return t->n_layers == 1 && t->layers[0].n <= BD_TRAIN_FUSED_MAX_WIDTH; }
+
+int check_batch(const bd_trainer_s* t, const float* X, int64_t ldx, const void* targets, int32_t B, const char* who) {
+    if (!t || !X || !targets) return fail(BD_EINVAL, std::string(who) + ": null argument");
+    if (B < 1 || B > t->max_batch) return fail(BD_EINVAL, std::string(who) + ": B must be in 1..max_batch");
+    if (ldx < BD_EMBEDDING_SIZE || ldx % 4 || (reinterpret_cast<uintptr_t>(X) & 15u))
+        return fail(BD_EINVAL, std::string(who) + ": X needs 16-byte alignment and ldx >= 1024, a multiple of 4");
+    return BD_OK;
+}
+
+void enqueue_forward(bd_trainer_s* t, const float* X, int64_t ldx, const int* rows, int B, hipStream_t stream) {
+    const float* a = X;
+    int64_t lda = ldx;
+    for (int l = 0; l < t->n_layers; ++l) {
+        const Layer& L = t->layers[l];
+        const int act = l + 1 < t->n_layers ? L.act : BD_HEAD_LINEAR;
+        hipLaunchKernelGGL(forward_kernel, dim3((B + 63) / 64, (L.n + 63) / 64), dim3(256), 0, stream, a, lda, l == 0 ? rows : nullptr,
+                           B, L.k, L.p, L.n, act, L.y, L.ld);
+        a = L.y;
+        lda = L.ld;
+    }
+}
+
+void enqueue_loss(bd_trainer_s* t, const void* targets, int B, float* loss_dev, bool accumulate, bool rows_done, hipStream_t stream) {
+    const Layer& L = t->layers[t->n_layers - 1];
+    const bool binary = t->loss == BD_TRAIN_BINARY;
+    if (!rows_done)
+        hipLaunchKernelGGL(loss_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, L.y, L.g, L.ld, B, L.n, t->loss, targets,
+                           1.0f / (binary ? (float)B * (float)L.n : (float)B), t->row_loss);
+    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, stream, t->row_loss, B, 1.0 / (binary ? (double)B * L.n : (double)B),
+                       loss_dev, accumulate ? t->acc : nullptr);
+}
+
+}  // namespace
+}  // namespace bd
+
+using bd::fail;
+
+extern "C" {
+
+int bd_train_abi_version(void) { return BD_TRAIN_ABI_VERSION; }
+
+int bd_trainer_create(int device, const bd_head_layer* layers, int32_t n_layers, int32_t loss, const bd_train_optimizer* opt,
+                      int32_t max_batch, bd_trainer* out) {
+    if (!out || !layers || !opt) return fail(BD_EINVAL, "bd_trainer_create: null argument");
+    *out = nullptr;
+    if (n_layers < 1 || n_layers > BD_HEAD_MAX_LAYERS) return fail(BD_EINVAL, "bd_trainer_create: n_layers must be in 1..8");
+    if (loss != BD_TRAIN_CATEGORICAL && loss != BD_TRAIN_BINARY) return fail(BD_EINVAL, "bd_trainer_create: unknown loss");
+    if (opt->kind != BD_TRAIN_SGD && opt->kind != BD_TRAIN_ADAM) return fail(BD_EINVAL, "bd_trainer_create: unknown optimizer");
+    if (!(opt->learning_rate > 0.0f) || !std::isfinite(opt->learning_rate))
+        return fail(BD_EINVAL, "bd_trainer_create: learning_rate must be positive and finite");
+    if (opt->kind == BD_TRAIN_ADAM && !(opt->beta_1 >= 0.0f && opt->beta_1 < 1.0f && opt->beta_2 >= 0.0f && opt->beta_2 < 1.0f &&
+                                        opt->epsilon > 0.0f))
+        return fail(BD_EINVAL, "bd_trainer_create: Adam needs 0 <= beta < 1 and epsilon > 0");
+    if (max_batch < 1 || max_batch > BD_TRAIN_MAX_BATCH) return fail(BD_EINVAL, "bd_trainer_create: max_batch must be in 1..65536");
+    for (int l = 0; l < n_layers; ++l) {
+        const bd_head_layer& L = layers[l];
+        const std::string where = "bd_trainer_create: layer " + std::to_string(l);
+        if (!L.kernel) return fail(BD_EINVAL, where + " has no kernel");
+        if (L.n_in != (l == 0 ? BD_EMBEDDING_SIZE : layers[l - 1].n_out))
+            return fail(BD_EINVAL, where + ": n_in must be 1024 for the first layer, the width before it for the others");
+        if (L.n_out < 1 || L.n_out > BD_HEAD_MAX_WIDTH) return fail(BD_EINVAL, where + ": n_out must be in 1..2048");
+        if (L.activation < BD_HEAD_LINEAR || L.activation > BD_HEAD_SOFTMAX || (L.activation == BD_HEAD_SOFTMAX && l + 1 < n_layers))
+            return fail(BD_EINVAL, where + ": hidden activations are linear, relu, sigmoid or tanh");
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(BD_ENODEVICE, "bd_trainer_create: no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= count) return fail(BD_ENODEVICE, "bd_trainer_create: device index out of range");
+    hipDeviceProp_t prop;
+    BDT_HIP(hipGetDeviceProperties(&prop, device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(BD_ENODEVICE, std::string("bd_trainer_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
+    BDT_HIP(hipSetDevice(device));
+
+    std::unique_ptr<bd_trainer_s> t(new bd_trainer_s);
+    t->device = device;
+    t->n_layers = n_layers;
+    t->loss = loss;
+    t->max_batch = max_batch;
+    t->opt = *opt;
+    const bool adam = opt->kind == BD_TRAIN_ADAM;
+    const int64_t slices = (max_batch + bd::kSliceRows - 1) / bd::kSliceRows;
+    // lay the pool out in floats, every piece on a 64-float boundary
+    auto up64 = [](int64_t v) { return (v + 63) / 64 * 64; };
+    int64_t total = 0, params_max = 0;
+    int64_t off_p[BD_HEAD_MAX_LAYERS], off_y[BD_HEAD_MAX_LAYERS];
+    for (int l = 0; l < n_layers; ++l) {
+        bd::Layer& L = t->layers[l];
+        L.k = layers[l].n_in;
+        L.n = layers[l].n_out;
+        L.act = layers[l].activation;
+        L.ld = (L.n + 31) / 32 * 32;
+        const int64_t np = (int64_t)L.k * L.n + L.n;
+        params_max = np > params_max ? np : params_max;
+        off_p[l] = total;
+        total += up64(np) * (adam ? 4 : 2);
+        off_y[l] = total;
+        total += up64((int64_t)max_batch * L.ld) * 2;
+    }
+    const int64_t off_ws = total;
+    t->ws_floats = slices * params_max;
+    total += up64(t->ws_floats);
+    const int64_t off_rl = total;
+    total += up64(max_batch);
+    const int64_t off_acc = total;
+    total += 64;
+    BDT_HIP(hipMalloc(&t->pool, (size_t)total * sizeof(float)));
+    hipError_t err = hipMemset(t->pool, 0, (size_t)total * sizeof(float));
+    for (int l = 0; l < n_layers && err == hipSuccess; ++l) {
+        bd::Layer& L = t->layers[l];
+        const int64_t np = (int64_t)L.k * L.n + L.n, step = up64(np);
+        L.p = t->pool + off_p[l];
+        L.grad = L.p + step;
+        L.m = adam ? L.p + 2 * step : nullptr;
+        L.v = adam ? L.p + 3 * step : nullptr;
+        L.y = t->pool + off_y[l];
+        L.g = L.y + up64((int64_t)max_batch * L.ld);
+        err = hipMemcpy(L.p, layers[l].kernel, (size_t)L.k * L.n * sizeof(float), hipMemcpyHostToDevice);
+        if (err == hipSuccess && layers[l].bias)
+            err = hipMemcpy(L.p + (size_t)L.k * L.n, layers[l].bias, (size_t)L.n * sizeof(float), hipMemcpyHostToDevice);
+    }
+    if (err != hipSuccess) {
+        (void)hipFree(t->pool);
+        return fail(BD_EHIP, std::string("bd_trainer_create: ") + hipGetErrorString(err));
+    }
+    t->ws = t->pool + off_ws;
+    t->row_loss = t->pool + off_rl;
+    t->acc = reinterpret_cast<double*>(t->pool + off_acc);
+    *out = t.release();
+    return BD_OK;
+}
+
+int bd_trainer_destroy(bd_trainer t) {
+    if (!t) return BD_OK;
+    (void)hipSetDevice(t->device);
+    (void)hipStreamSynchronize(t->last);
+    if (t->pool) (void)hipFree(t->pool);
+    delete t;
+    return BD_OK;
+}
+
+int bd_trainer_set_fusion(bd_trainer t, int32_t fused) {
+    if (!t) return fail(BD_EINVAL, "bd_trainer_set_fusion: null handle");
+    t->fused = fused != 0;
+    return BD_OK;
+}
+
+int bd_trainer_step(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, int32_t B, void* stream_) {
+    const int rc = bd::check_batch(t, X, ldx, targets, B, "bd_trainer_step");
+    if (rc < 0) return rc;
+    BDT_HIP(hipSetDevice(t->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    t->last = stream;
+    const int slices = (B + bd::kSliceRows - 1) / bd::kSliceRows;
+    const bool binary = t->loss == BD_TRAIN_BINARY;
+    t->step += 1;
+    bd::Update u{t->opt.kind, t->opt.learning_rate, t->opt.beta_1, t->opt.beta_2, t->opt.epsilon, 0.0f};
+    if (u.kind == BD_TRAIN_ADAM)
+        u.lr_t = (float)((double)u.lr * std::sqrt(1.0 - std::pow((double)u.b2, (double)t->step)) /
+                         (1.0 - std::pow((double)u.b1, (double)t->step)));
+    const bool fused = t->fused && bd::fusable(t);
+    if (fused) {
+        const bd::Layer& L = t->layers[0];
+        hipLaunchKernelGGL(bd::fused_step_kernel, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, L.p, L.n, L.y, L.g, L.ld,
+                           t->loss, targets, 1.0f / (binary ? (float)B * (float)L.n : (float)B), t->row_loss, t->ws);
+    } else {
+        bd::enqueue_forward(t, X, ldx, rows, B, stream);
+    }
+    bd::enqueue_loss(t, targets, B, nullptr, true, fused, stream);
+    for (int l = t->n_layers - 1; l >= 0; --l) {
+        const bd::Layer& L = t->layers[l];
+        const int n = L.k * L.n + L.n;
+        if (!fused) {
+            const float* a = l == 0 ? X : t->layers[l - 1].y;
+            const int64_t lda = l == 0 ? ldx : t->layers[l - 1].ld;
+            const int tiles = (L.k + 31) / 32 * ((L.n + 31) / 32);
+            hipLaunchKernelGGL(bd::weight_grad_kernel, dim3((tiles + 3) / 4, slices), dim3(256), 0, stream, a, lda,
+                               l == 0 ? rows : nullptr, B, L.k, L.g, L.ld, L.n, t->ws);
+        }
+        if (l > 0) {                                     // with this layer's weights as the forward pass saw them
+            const bd::Layer& Lp = t->layers[l - 1];
+            hipLaunchKernelGGL(bd::input_grad_kernel, dim3((B + 63) / 64, (L.k + 63) / 64), dim3(256), 0, stream, L.g, L.ld, B, L.k,
+                               L.p, L.n, Lp.y, Lp.act, Lp.g, Lp.ld);
+        }
+        hipLaunchKernelGGL(bd::apply_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, t->ws, slices, n, L.grad, L.p, L.m, L.v, u);
+    }
+    BDT_HIP(hipGetLastError());
+    return BD_OK;
+}
+
+int bd_trainer_loss(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, int32_t B, float* loss_dev,
+                    void* stream_) {
+    const int rc = bd::check_batch(t, X, ldx, targets, B, "bd_trainer_loss");
+    if (rc < 0) return rc;
+    if (!loss_dev) return fail(BD_EINVAL, "bd_trainer_loss: null loss_dev");
+    BDT_HIP(hipSetDevice(t->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    t->last = stream;
+    bd::enqueue_forward(t, X, ldx, rows, B, stream);
+    bd::enqueue_loss(t, targets, B, loss_dev, false, false, stream);
+    BDT_HIP(hipGetLastError());
+    return BD_OK;
+}
+
+static int read_pair(bd_trainer t, int32_t layer, bool grad, float* w_host, float* b_host, const char* who) {
+    if (!t || layer < 0 || layer >= t->n_layers) return fail(BD_EINVAL, std::string(who) + ": no such layer");
+    BDT_HIP(hipSetDevice(t->device));
+    BDT_HIP(hipStreamSynchronize(t->last));
+    const bd::Layer& L = t->layers[layer];
+    const float* src = grad ? L.grad : L.p;
+    if (w_host) BDT_HIP(hipMemcpy(w_host, src, (size_t)L.k * L.n * sizeof(float), hipMemcpyDeviceToHost));
+    if (b_host) BDT_HIP(hipMemcpy(b_host, src + (size_t)L.k * L.n, (size_t)L.n * sizeof(float), hipMemcpyDeviceToHost));
+    return BD_OK;
+}
+
+int bd_trainer_gradients(bd_trainer t, int32_t layer, float* dW_host, float* db_host) {
+    return read_pair(t, layer, true, dW_host, db_host, "bd_trainer_gradients");
+}
+
+int bd_trainer_read(bd_trainer t, int32_t layer, float* kernel_host, float* bias_host) {
+    return read_pair(t, layer, false, kernel_host, bias_host, "bd_trainer_read");
+}
+
+int bd_trainer_logits(bd_trainer t, int32_t B, float* logits_host) {
+    if (!t || !logits_host || B < 1 || B > t->max_batch) return fail(BD_EINVAL, "bd_trainer_logits: bad argument");
+    BDT_HIP(hipSetDevice(t->device));
+    BDT_HIP(hipStreamSynchronize(t->last));
+    const bd::Layer& L = t->layers[t->n_layers - 1];
+    BDT_HIP(hipMemcpy2D(logits_host, (size_t)L.n * sizeof(float), L.y, (size_t)L.ld * sizeof(float), (size_t)L.n * sizeof(float), B,
+                        hipMemcpyDeviceToHost));
+    return BD_OK;
+}
+
+int bd_trainer_mean_loss(bd_trainer t, int32_t reset, float* mean_host) {
+    if (!t || !mean_host) return fail(BD_EINVAL, "bd_trainer_mean_loss: null argument");
+    BDT_HIP(hipSetDevice(t->device));
+    BDT_HIP(hipStreamSynchronize(t->last));
+    double acc[2] = {0.0, 0.0};
+    BDT_HIP(hipMemcpy(acc, t->acc, sizeof(acc), hipMemcpyDeviceToHost));
+    *mean_host = acc[1] > 0.0 ? (float)(acc[0] / acc[1]) : 0.0f;
+    if (reset) BDT_HIP(hipMemset(t->acc, 0, sizeof(acc)));
+    return BD_OK;
+}
+
+int64_t bd_trainer_workspace_floats(bd_trainer t) {
+    if (!t) return fail(BD_EINVAL, "bd_trainer_workspace_floats: null handle");
+    return t->ws_floats;
+}
+
+int bd_trainer_workspace_fill(bd_trainer t, uint32_t pattern) {
+    if (!t) return fail(BD_EINVAL, "bd_trainer_workspace_fill: null handle");
+    BDT_HIP(hipSetDevice(t->device));
+    BDT_HIP(hipStreamSynchronize(t->last));
+    hipLaunchKernelGGL(bd::fill_kernel, dim3(256), dim3(256), 0, t->last, reinterpret_cast<uint32_t*>(t->ws), (size_t)t->ws_floats,
+                       pattern);
+    BDT_HIP(hipGetLastError());
+    BDT_HIP(hipStreamSynchronize(t->last));
+    return BD_OK;
+}
+
+int bd_trainer_workspace_read(bd_trainer t, float* host, int64_t floats) {
+    if (!t || !host || floats < 0 || floats > t->ws_floats) return fail(BD_EINVAL, "bd_trainer_workspace_read: bad argument");
+    BDT_HIP(hipSetDevice(t->device));
+    BDT_HIP(hipStreamSynchronize(t->last));
+    BDT_HIP(hipMemcpy(host, t->ws, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost));
+    return BD_OK;
+}
+
+}  // extern "C"

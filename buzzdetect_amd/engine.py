@@ -196,6 +196,20 @@ class DeviceResult:
                 self._host = self.tensor.cpu().numpy()
             return self._host
 
+    def device_tensor(self) -> torch.Tensor:
+        """The rows on the device, final: waits for the launch set's range word and recomputes flagged rows as ``numpy()``
+        does, without the copy to the host (``train.fit_head`` reads embeddings where they are)."""
+        with self._lock:
+            if self._host is None:
+                if self._verdict is not None and self._verdict.wait() and self._redo is not None:
+                    self.tensor = self._redo()
+                    if self._engine is not None:
+                        self._engine.overflow_reruns += 1
+                elif self._verdict is None:
+                    self._done.synchronize()
+                self._redo = None
+            return self.tensor
+
     def __array__(self, dtype=None, copy=None):
         a = self.numpy()
         return a.astype(dtype) if dtype is not None else a
