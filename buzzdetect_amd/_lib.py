@@ -192,7 +192,7 @@ ANYRATE_PROTOTYPES = {
     "bd_resample_any_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
-TRAIN_ABI_VERSION = 1
+TRAIN_ABI_VERSION = 2
 TRAIN_SLICE_ROWS = 256
 TRAIN_FUSED_MAX_WIDTH = 64
 TRAIN_MAX_BATCH = 65536
@@ -213,6 +213,14 @@ TRAIN_PROTOTYPES = {
     "bd_trainer_destroy": (C.c_int, [C.c_void_p]),
     "bd_trainer_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "bd_trainer_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_trainer_step_weighted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p]),
+    "bd_trainer_loss_weighted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p]),
+    "bd_trainer_set_weight_decay": (C.c_int, [C.c_void_p, C.c_float]),
+    "bd_trainer_set_learning_rate": (C.c_int, [C.c_void_p, C.c_float]),
+    "bd_trainer_snapshot": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bd_trainer_restore": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bd_trainer_gradients": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "bd_trainer_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "bd_trainer_logits": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

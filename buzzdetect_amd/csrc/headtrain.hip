@@ -19,6 +19,12 @@
 // fused_step_kernel (one layer, n_out <= 64): a workgroup of eight waves owns a slice and calls the same three routines -
 // logits of its 256 rows, their deltas, the slice's dW partial - so the partial's second walk over the slice's rows of X finds
 // them in the cache the first walk filled: X comes from HBM once per step.
+//
+// Row weights (bd_trainer_step_weighted): loss_row<true> reads w_r beside the row's target and uses scale_r = inv * w_r where
+// the plain pass uses inv, and stores w_r * loss_r; loss_row<false> is the plain pass, instruction for instruction.  The
+// weight is a kernel argument, the same for every lane: no lane leaves or branches apart in front of the fused kernel's
+// barriers.  Decoupled weight decay is apply_kernel's: p = p - (lr wd) p on a layer's kernel elements (never its bias), two
+// roundings, before the optimizer's update is subtracted from p.
 #include "bd_internal.h"
 
 #include <cmath>
@@ -227,9 +233,17 @@ __device__ __forceinline__ void bias_grad_tile(const float* G, int ldg, int r0, 
 
 // One row of the last layer: its loss and the delta of its logits.  One wave; lane l takes columns l, l + 64, ... in ascending
 // order and the 64 partial results meet in a butterfly, the same order for every row wherever it sits.
+// kWeighted: the row counts w_r = row_w[row] times: scale_r = inv * w_r (one product) takes inv's place in the delta and the
+// row's loss is stored as w_r * loss_r (one product).  Without it row_w is not read.
+template <bool kWeighted>
 __device__ __forceinline__ void loss_row(const float* z, float* g, int C, int loss,
-                                         const void* __restrict__ targets, int row, float inv, float* __restrict__ row_loss,
-                                         int lane) {
+                                         const void* __restrict__ targets, const float* __restrict__ row_w, int row, float inv,
+                                         float* __restrict__ row_loss, int lane) {
+    float w = 1.0f;
+    if (kWeighted) {
+        w = row_w[row];
+        inv = inv * w;
+    }
     if (loss == BD_TRAIN_CATEGORICAL) {
         const int label = reinterpret_cast<const int*>(targets)[row];
         float m = -INFINITY;
@@ -241,7 +255,10 @@ __device__ __forceinline__ void loss_row(const float* z, float* g, int C, int lo
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
         for (int c = lane; c < C; c += 64) g[c] = (expf(z[c] - m) / sum - (c == label ? 1.0f : 0.0f)) * inv;
-        if (lane == 0) row_loss[row] = (m + logf(sum)) - z[min(max(label, 0), C - 1)];
+        if (lane == 0) {
+            const float l = (m + logf(sum)) - z[min(max(label, 0), C - 1)];
+            row_loss[row] = kWeighted ? w * l : l;
+        }
     } else {
         const float* t = reinterpret_cast<const float*>(targets) + (size_t)row * C;
         float sum = 0.0f;
@@ -254,7 +271,7 @@ __device__ __forceinline__ void loss_row(const float* z, float* g, int C, int lo
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-        if (lane == 0) row_loss[row] = sum;
+        if (lane == 0) row_loss[row] = kWeighted ? w * sum : sum;
     }
 }
 
@@ -293,20 +310,24 @@ __global__ __launch_bounds__(256) void weight_grad_kernel(const float* __restric
     if (tk == 0) bias_grad_tile(G, ldg, r0, r1, N, part + (size_t)K * N, tn, lane);
 }
 
+template <bool kWeighted>
 __global__ __launch_bounds__(256) void loss_rows_kernel(const float* __restrict__ Z, float* __restrict__ G, int ld, int B, int C,
-                                                         int loss, const void* __restrict__ targets, float inv,
+                                                         int loss, const void* __restrict__ targets,
+                                                         const float* __restrict__ row_w, float inv,
                                                          float* __restrict__ row_loss) {
     const int row = 4 * blockIdx.x + (threadIdx.x >> 6);
     if (row >= B) return;
-    loss_row(Z + (size_t)row * ld, G + (size_t)row * ld, C, loss, targets, row, inv, row_loss, threadIdx.x & 63);
+    loss_row<kWeighted>(Z + (size_t)row * ld, G + (size_t)row * ld, C, loss, targets, row_w, row, inv, row_loss, threadIdx.x & 63);
 }
 
-// One layer of at most 64 outputs; grid = slices, eight waves.  Z / G [B][64].
+// One layer of at most 64 outputs; grid = slices, eight waves.  Z / G [B][64].  Every wave reaches both barriers: the loops
+// around them end on their bounds, and row_w changes what a row's pass computes, not which waves run it.
+template <bool kWeighted>
 __global__ __launch_bounds__(512) void fused_step_kernel(const float* __restrict__ X, int64_t ldx, const int* __restrict__ rows,
                                                            int B, int K, const float* __restrict__ P, int N, float* Z,
                                                            float* G, int ld, int loss,
-                                                           const void* __restrict__ targets, float inv, float* __restrict__ row_loss,
-                                                           float* __restrict__ ws) {
+                                                           const void* __restrict__ targets, const float* __restrict__ row_w,
+                                                           float inv, float* __restrict__ row_loss, float* __restrict__ ws) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int slice = blockIdx.x, r0 = slice * kSliceRows, r1 = min(B, r0 + kSliceRows);
     const int tiles_n = (N + 31) / 32;
@@ -316,7 +337,7 @@ __global__ __launch_bounds__(512) void fused_step_kernel(const float* __restrict
     }
     __syncthreads();                                     // the slice's logits, written above by this workgroup
     for (int row = r0 + wave; row < r1; row += 8)
-        loss_row(Z + (size_t)row * ld, G + (size_t)row * ld, N, loss, targets, row, inv, row_loss, lane);
+        loss_row<kWeighted>(Z + (size_t)row * ld, G + (size_t)row * ld, N, loss, targets, row_w, row, inv, row_loss, lane);
     __syncthreads();                                     // the slice's deltas
     float* part = ws + (size_t)slice * ((size_t)K * N + N);
     const int tiles = (K + 31) / 32 * tiles_n;
@@ -354,9 +375,18 @@ struct Update {
     int kind;
     float lr, b1, b2, eps;
     float lr_t;                     // Adam: lr sqrt(1 - b2^t) / (1 - b1^t) of this step
+    float decay;                    // lr * weight_decay of this step, one float32 product; 0 = none
+    int decay_n;                    // the leading elements it applies to: the layer's kernel, not the bias behind it
 };
 
-// element i of a layer's [W | b]: the slices' partials in ascending order, then the optimizer
+// p - decay * p in two roundings (no fused multiply-add: the host restates it as a product and a difference)
+__device__ __forceinline__ float decayed(float p, float decay) {
+#pragma clang fp contract(off)
+    const float d = decay * p;
+    return p - d;
+}
+
+// element i of a layer's [W | b]: the slices' partials in ascending order, then the decay (kernel elements only), then the optimizer
 __global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ ws, int slices, int n, float* __restrict__ grad,
                                                      float* __restrict__ P, float* __restrict__ m, float* __restrict__ v, Update u) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -364,14 +394,17 @@ __global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ ws
     float g = ws[i];
     for (int s = 1; s < slices; ++s) g += ws[(size_t)s * n + i];
     grad[i] = g;
+    float p = P[i];
+    if (u.decay != 0.0f && i < u.decay_n) p = decayed(p, u.decay);
     if (u.kind == BD_TRAIN_ADAM) {
         const float mi = u.b1 * m[i] + (1.0f - u.b1) * g;
         const float vi = u.b2 * v[i] + (1.0f - u.b2) * (g * g);
         m[i] = mi;
         v[i] = vi;
-        P[i] = P[i] - u.lr_t * mi / (sqrtf(vi) + u.eps);
+        P[i] = p - u.lr_t * mi / (sqrtf(vi) + u.eps);
     } else {
-        P[i] = P[i] - u.lr * g;
+        P[i] = __builtin_fmaf(-u.lr, g, p);              // p - lr g in one rounding, as it has always been compiled: spelled out so that
+                                                         // the code around it cannot change the bits
     }
 }
 
@@ -393,6 +426,7 @@ int fail(int code, const std::string& msg) {
 struct Layer {
     int k, n, act, ld;              // ld = round_up(n, 32): row stride of y and g
     float *p, *grad, *m, *v;        // [k n + n] each: W then b (m, v: Adam only)
+    float* snap;                    // [k n + n]: the parameters as bd_trainer_snapshot found them
     float *y, *g;                   // [max_batch][ld]: activations (the last layer's: logits) and d loss / d pre-activation
 };
 
@@ -404,6 +438,8 @@ struct bd_trainer_s {
     bd_train_optimizer opt{};
     int64_t step = 0;
     bool fused = true;
+    float weight_decay = 0.0f;
+    bool has_snapshot = false;
     bd::Layer layers[BD_HEAD_MAX_LAYERS]{};
     float* pool = nullptr;          // one allocation behind every pointer above and below
     float* ws = nullptr;            // [slices][k n + n] of the layer at work
@@ -439,12 +475,19 @@ void enqueue_forward(bd_trainer_s* t, const float* X, int64_t ldx, const int* ro
     }
 }
 
-void enqueue_loss(bd_trainer_s* t, const void* targets, int B, float* loss_dev, bool accumulate, bool rows_done, hipStream_t stream) {
+void enqueue_loss(bd_trainer_s* t, const void* targets, const float* row_w, int B, float* loss_dev, bool accumulate, bool rows_done,
+                  hipStream_t stream) {
     const Layer& L = t->layers[t->n_layers - 1];
     const bool binary = t->loss == BD_TRAIN_BINARY;
-    if (!rows_done)
-        hipLaunchKernelGGL(loss_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, L.y, L.g, L.ld, B, L.n, t->loss, targets,
-                           1.0f / (binary ? (float)B * (float)L.n : (float)B), t->row_loss);
+    if (!rows_done) {
+        const float inv = 1.0f / (binary ? (float)B * (float)L.n : (float)B);
+        if (row_w)
+            hipLaunchKernelGGL(loss_rows_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, stream, L.y, L.g, L.ld, B, L.n, t->loss,
+                               targets, row_w, inv, t->row_loss);
+        else
+            hipLaunchKernelGGL(loss_rows_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, stream, L.y, L.g, L.ld, B, L.n, t->loss,
+                               targets, row_w, inv, t->row_loss);
+    }
     hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, stream, t->row_loss, B, 1.0 / (binary ? (double)B * L.n : (double)B),
                        loss_dev, accumulate ? t->acc : nullptr);
 }
@@ -512,7 +555,7 @@ int bd_trainer_create(int device, const bd_head_layer* layers, int32_t n_layers,
         const int64_t np = (int64_t)L.k * L.n + L.n;
         params_max = np > params_max ? np : params_max;
         off_p[l] = total;
-        total += up64(np) * (adam ? 4 : 2);
+        total += up64(np) * (adam ? 5 : 3);
         off_y[l] = total;
         total += up64((int64_t)max_batch * L.ld) * 2;
     }
@@ -532,6 +575,7 @@ int bd_trainer_create(int device, const bd_head_layer* layers, int32_t n_layers,
         L.grad = L.p + step;
         L.m = adam ? L.p + 2 * step : nullptr;
         L.v = adam ? L.p + 3 * step : nullptr;
+        L.snap = L.p + (adam ? 4 : 2) * step;
         L.y = t->pool + off_y[l];
         L.g = L.y + up64((int64_t)max_batch * L.ld);
         err = hipMemcpy(L.p, layers[l].kernel, (size_t)L.k * L.n * sizeof(float), hipMemcpyHostToDevice);
@@ -564,28 +608,37 @@ int bd_trainer_set_fusion(bd_trainer t, int32_t fused) {
     return BD_OK;
 }
 
-int bd_trainer_step(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, int32_t B, void* stream_) {
-    const int rc = bd::check_batch(t, X, ldx, targets, B, "bd_trainer_step");
+// bd_trainer_step (row_w == nullptr: the plain kernels) and bd_trainer_step_weighted
+static int do_step(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, const float* row_w, int32_t B,
+                   void* stream_, const char* who) {
+    const int rc = bd::check_batch(t, X, ldx, targets, B, who);
     if (rc < 0) return rc;
+    if (reinterpret_cast<uintptr_t>(row_w) & 3u) return fail(BD_EINVAL, std::string(who) + ": row_weights is not aligned to a float");
     BDT_HIP(hipSetDevice(t->device));
     hipStream_t stream = (hipStream_t)stream_;
     t->last = stream;
     const int slices = (B + bd::kSliceRows - 1) / bd::kSliceRows;
     const bool binary = t->loss == BD_TRAIN_BINARY;
     t->step += 1;
-    bd::Update u{t->opt.kind, t->opt.learning_rate, t->opt.beta_1, t->opt.beta_2, t->opt.epsilon, 0.0f};
+    bd::Update u{t->opt.kind, t->opt.learning_rate, t->opt.beta_1, t->opt.beta_2, t->opt.epsilon, 0.0f,
+                 t->weight_decay != 0.0f ? t->opt.learning_rate * t->weight_decay : 0.0f, 0};
     if (u.kind == BD_TRAIN_ADAM)
         u.lr_t = (float)((double)u.lr * std::sqrt(1.0 - std::pow((double)u.b2, (double)t->step)) /
                          (1.0 - std::pow((double)u.b1, (double)t->step)));
     const bool fused = t->fused && bd::fusable(t);
     if (fused) {
         const bd::Layer& L = t->layers[0];
-        hipLaunchKernelGGL(bd::fused_step_kernel, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, L.p, L.n, L.y, L.g, L.ld,
-                           t->loss, targets, 1.0f / (binary ? (float)B * (float)L.n : (float)B), t->row_loss, t->ws);
+        const float inv = 1.0f / (binary ? (float)B * (float)L.n : (float)B);
+        if (row_w)
+            hipLaunchKernelGGL(bd::fused_step_kernel<true>, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, L.p, L.n, L.y,
+                               L.g, L.ld, t->loss, targets, row_w, inv, t->row_loss, t->ws);
+        else
+            hipLaunchKernelGGL(bd::fused_step_kernel<false>, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, L.p, L.n, L.y,
+                               L.g, L.ld, t->loss, targets, row_w, inv, t->row_loss, t->ws);
     } else {
         bd::enqueue_forward(t, X, ldx, rows, B, stream);
     }
-    bd::enqueue_loss(t, targets, B, nullptr, true, fused, stream);
+    bd::enqueue_loss(t, targets, row_w, B, nullptr, true, fused, stream);
     for (int l = t->n_layers - 1; l >= 0; --l) {
         const bd::Layer& L = t->layers[l];
         const int n = L.k * L.n + L.n;
@@ -601,24 +654,87 @@ int bd_trainer_step(bd_trainer t, const float* X, int64_t ldx, const int32_t* ro
             hipLaunchKernelGGL(bd::input_grad_kernel, dim3((B + 63) / 64, (L.k + 63) / 64), dim3(256), 0, stream, L.g, L.ld, B, L.k,
                                L.p, L.n, Lp.y, Lp.act, Lp.g, Lp.ld);
         }
+        u.decay_n = L.k * L.n;
         hipLaunchKernelGGL(bd::apply_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, t->ws, slices, n, L.grad, L.p, L.m, L.v, u);
     }
     BDT_HIP(hipGetLastError());
     return BD_OK;
 }
 
-int bd_trainer_loss(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, int32_t B, float* loss_dev,
-                    void* stream_) {
-    const int rc = bd::check_batch(t, X, ldx, targets, B, "bd_trainer_loss");
+int bd_trainer_step(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, int32_t B, void* stream) {
+    return do_step(t, X, ldx, rows, targets, nullptr, B, stream, "bd_trainer_step");
+}
+
+int bd_trainer_step_weighted(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets,
+                             const float* row_weights, int32_t B, void* stream) {
+    return do_step(t, X, ldx, rows, targets, row_weights, B, stream, "bd_trainer_step_weighted");
+}
+
+static int do_loss(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, const float* row_w, int32_t B,
+                   float* loss_dev, void* stream_, const char* who) {
+    const int rc = bd::check_batch(t, X, ldx, targets, B, who);
     if (rc < 0) return rc;
-    if (!loss_dev) return fail(BD_EINVAL, "bd_trainer_loss: null loss_dev");
+    if (reinterpret_cast<uintptr_t>(row_w) & 3u) return fail(BD_EINVAL, std::string(who) + ": row_weights is not aligned to a float");
+    if (!loss_dev) return fail(BD_EINVAL, std::string(who) + ": null loss_dev");
     BDT_HIP(hipSetDevice(t->device));
     hipStream_t stream = (hipStream_t)stream_;
     t->last = stream;
     bd::enqueue_forward(t, X, ldx, rows, B, stream);
-    bd::enqueue_loss(t, targets, B, loss_dev, false, false, stream);
+    bd::enqueue_loss(t, targets, row_w, B, loss_dev, false, false, stream);
     BDT_HIP(hipGetLastError());
     return BD_OK;
+}
+
+int bd_trainer_loss(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, int32_t B, float* loss_dev,
+                    void* stream) {
+    return do_loss(t, X, ldx, rows, targets, nullptr, B, loss_dev, stream, "bd_trainer_loss");
+}
+
+int bd_trainer_loss_weighted(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets,
+                             const float* row_weights, int32_t B, float* loss_dev, void* stream) {
+    return do_loss(t, X, ldx, rows, targets, row_weights, B, loss_dev, stream, "bd_trainer_loss_weighted");
+}
+
+int bd_trainer_set_weight_decay(bd_trainer t, float weight_decay) {
+    if (!t) return fail(BD_EINVAL, "bd_trainer_set_weight_decay: null handle");
+    if (!(weight_decay >= 0.0f) || !std::isfinite(weight_decay))
+        return fail(BD_EINVAL, "bd_trainer_set_weight_decay: weight_decay must be finite and not negative");
+    t->weight_decay = weight_decay;
+    return BD_OK;
+}
+
+int bd_trainer_set_learning_rate(bd_trainer t, float learning_rate) {
+    if (!t) return fail(BD_EINVAL, "bd_trainer_set_learning_rate: null handle");
+    if (!(learning_rate > 0.0f) || !std::isfinite(learning_rate))
+        return fail(BD_EINVAL, "bd_trainer_set_learning_rate: learning_rate must be positive and finite");
+    t->opt.learning_rate = learning_rate;
+    return BD_OK;
+}
+
+// parameters -> snapshot (to_snapshot) or back, layer by layer, on the caller's stream
+static int copy_parameters(bd_trainer t, bool to_snapshot, void* stream_) {
+    BDT_HIP(hipSetDevice(t->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    t->last = stream;
+    for (int l = 0; l < t->n_layers; ++l) {
+        const bd::Layer& L = t->layers[l];
+        const size_t bytes = ((size_t)L.k * L.n + L.n) * sizeof(float);
+        BDT_HIP(hipMemcpyAsync(to_snapshot ? L.snap : L.p, to_snapshot ? L.p : L.snap, bytes, hipMemcpyDeviceToDevice, stream));
+    }
+    return BD_OK;
+}
+
+int bd_trainer_snapshot(bd_trainer t, void* stream) {
+    if (!t) return fail(BD_EINVAL, "bd_trainer_snapshot: null handle");
+    const int rc = copy_parameters(t, true, stream);
+    if (rc == BD_OK) t->has_snapshot = true;
+    return rc;
+}
+
+int bd_trainer_restore(bd_trainer t, void* stream) {
+    if (!t) return fail(BD_EINVAL, "bd_trainer_restore: null handle");
+    if (!t->has_snapshot) return fail(BD_EINVAL, "bd_trainer_restore: no snapshot was taken (bd_trainer_snapshot)");
+    return copy_parameters(t, false, stream);
 }
 
 static int read_pair(bd_trainer t, int32_t layer, bool grad, float* w_host, float* b_host, const char* who) {

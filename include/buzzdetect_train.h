@@ -15,6 +15,27 @@
  *   BD_TRAIN_BINARY        sigmoid cross-entropy from logits, float multi-hot targets [B][C], mean over batch x classes:
  *                          loss_rc = max(z, 0) - z t + log1p(exp(-|z|)),            dz = (sigmoid(z) - t) / (B C)
  *
+ * Row weights (bd_trainer_step_weighted / bd_trainer_loss_weighted; Keras's sample_weight with sum_over_batch_size: the sums
+ * are divided by B, not by the sum of the weights).  Row r counts w_r times, w_r >= 0 a float in batch order:
+ *   categorical   loss = (1/B) sum_r w_r loss_r,             dz_r  = w_r (softmax(z_r) - onehot_r) / B
+ *   binary        loss = (1/(B C)) sum_r w_r sum_c loss_rc,  dz_rc = w_r (sigmoid(z_rc) - t_rc) / (B C)
+ * in this float32 arithmetic: scale_r = inv * w_r (one product; inv = 1/B or 1/(B C)), the delta is (...) * scale_r, and the
+ * row's loss is stored as w_r * loss_r (one product).  Class weights are row weights the caller builds: w_r = class_weight
+ * [label_r].  Without weights (NULL) the plain kernels run, instruction for instruction; weights of 1.0f give their bits.
+ *
+ * Weight decay (bd_trainer_set_weight_decay) is decoupled, as AdamW's: decay = lr * weight_decay, one float32 product on the
+ * host per step; an element p of a layer's kernel - never of its bias - becomes p - decay * p (a product, then a difference)
+ * and the optimizer's update of the step is subtracted from that.  It is not a term of the loss: neither the loss nor the
+ * gradients read back change.  0 (the default) is no decay at all: the branch is not taken.
+ *
+ * Order within a step: forward, row losses and deltas (weighted), backward, then per element the sum of the slices' partials,
+ * the decay, the SGD or Adam update.  The learning rate of a step is the one set when it is enqueued
+ * (bd_trainer_set_learning_rate: a schedule is the caller's loop).
+ *
+ * Snapshot (bd_trainer_snapshot / bd_trainer_restore): a device-to-device copy of every layer's parameters into a second
+ * buffer of the trainer's and back, enqueued like a step.  Adam's slots and the step count are not part of it: it exists to
+ * hand back the best weights seen, not to resume.
+ *
  * Arithmetic: exact float32 on v_mfma_f32_32x32x2_f32 with f32 accumulate, the forward pass in headmlp.hip's operand map
  * and k order (a trained head gives the engine the logits the trainer saw).  Hidden derivatives come from the stored
  * activations.  Three products per layer: Y = act(A W + b), dA = (dY * act') W^T, dW = A^T (dY * act'), db its column sum.
@@ -30,8 +51,8 @@
  * targets and loss_dev owned by the caller, 16-byte aligned X with ldx a multiple of 4.  The trainer owns the parameters,
  * the optimizer's slots and its workspace.  A handle is not thread-safe.
  *
- * Out of scope: class or sample weights, dropout, regularisation, learning-rate schedules, early stopping, more than one
- * device, and anything below the embedding.
+ * Out of scope: dropout, penalties added to the loss (L1 / L2), a per-class pos_weight for the binary loss, focal loss and
+ * label smoothing, resuming from a snapshot, more than one device, and anything below the embedding.
  */
 #ifndef BUZZDETECT_TRAIN_H
 #define BUZZDETECT_TRAIN_H
@@ -44,7 +65,7 @@
 extern "C" {
 #endif
 
-#define BD_TRAIN_ABI_VERSION 1
+#define BD_TRAIN_ABI_VERSION 2
 #define BD_TRAIN_SLICE_ROWS 256          /* rows of the batch per dW partial (fixed: part of the results' bits) */
 #define BD_TRAIN_FUSED_MAX_WIDTH 64      /* widest one-layer stack that takes the fused kernel */
 #define BD_TRAIN_MAX_BATCH 65536
@@ -86,6 +107,24 @@ BD_API int bd_trainer_step(bd_trainer t, const float* X, int64_t ldx, const int3
 /* Forward pass and loss only: writes the batch's mean loss to loss_dev[0] (device float). */
 BD_API int bd_trainer_loss(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, int32_t B,
                            float* loss_dev, void* stream);
+
+/* The same two calls with a weight per row: row_weights is device float[B] in batch order, like targets (finite, >= 0: the
+ * caller vouches for it); NULL is bd_trainer_step / bd_trainer_loss.  bd_trainer_mean_loss then reports the weighted loss
+ * per row (the running sum still counts B rows a step). */
+BD_API int bd_trainer_step_weighted(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets,
+                                    const float* row_weights, int32_t B, void* stream);
+BD_API int bd_trainer_loss_weighted(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets,
+                                    const float* row_weights, int32_t B, float* loss_dev, void* stream);
+
+/* Host-side settings of the steps enqueued from now on; nothing is enqueued.  weight_decay >= 0 and finite (0: none; it
+ * applies to kernels only), learning_rate > 0 and finite (it replaces bd_train_optimizer.learning_rate). */
+BD_API int bd_trainer_set_weight_decay(bd_trainer t, float weight_decay);
+BD_API int bd_trainer_set_learning_rate(bd_trainer t, float learning_rate);
+
+/* Copy every layer's parameters to the trainer's snapshot buffer / back from it, on `stream`, without synchronisation.
+ * bd_trainer_restore before any bd_trainer_snapshot is BD_EINVAL. */
+BD_API int bd_trainer_snapshot(bd_trainer t, void* stream);
+BD_API int bd_trainer_restore(bd_trainer t, void* stream);
 
 /* Synchronous reads (they wait for the stream of the trainer's last call).  Gradients are those of the last step;
  * kernel_host / dW_host [n_in][n_out], bias_host / db_host [n_out]; either may be NULL. */
