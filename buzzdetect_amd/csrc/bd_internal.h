@@ -142,14 +142,17 @@ void anyrate_table(const AnyratePlan& plan, std::vector<float>* table);
 void launch_anyrate(const void* in, bool s16, int64_t n_in, int channels, const AnyratePlan& plan, const float* table,
                     float* out, int64_t n_out, hipStream_t stream);
 
-// ---- launchers (each enqueues exactly one kernel on `stream`) ----
+// ---- launchers (each enqueues exactly one kernel on `stream`), by the file that defines them ----
+// ---- frontend.hip ----
 void launch_logmel(const float* pcm, int64_t n_valid, int64_t n_frames, float* logmel,
                    const FeTables* tables, hipStream_t stream);
 void launch_resample(const void* in, bool s16, int64_t n_in, int channels, const float* taps, int half, int up,
                      int down, float* out, int64_t n_out, hipStream_t stream);
-bool resample_span_fits(int half, int up, int down);       // frontend.hip: can resample_kernel stage one output's span?
+bool resample_span_fits(int half, int up, int down);       // can resample_kernel stage one output's span?
 void launch_patches(const float* logmel, int64_t n_windows, int patch_step, float* patches,
                     hipStream_t stream);
+
+// ---- cnn.hip: one kernel per op, and the shape rules of the 1x1 convolutions ----
 void launch_conv1(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* w9x32,
                   const float* b32, float* out, hipStream_t stream);
 void launch_depthwise(const float* in, float* out, int windows, const SepLayer& L, hipStream_t stream);
@@ -162,55 +165,81 @@ int launch_pointwise_f16x3_variant(const float* A, const void* Whi, const void* 
 void launch_scale_copy(const float* src, float* dst, int64_t n, float factor, hipStream_t stream);
 bool launch_pointwise_next_dw_f32(const float* in, float* out, int windows, const SepLayer& L, const SepLayer& Ln,
                                   hipStream_t stream);
+// layer L + the stride-2 depthwise of `next`: launch_l4_window_next_dw or launch_sep_ws_next_dw, whichever takes the shape
+bool launch_separable_fused_next_dw(const float* in, float* out, int windows, const SepLayer& L, const SepLayer& next,
+                                    hipStream_t stream);
+void launch_pool_head(const float* act, int windows, const float* head_wt, const float* head_b,
+                      int n_classes, float* emb, float* logits, hipStream_t stream);
+void launch_head(const float* pooled, int windows, const float* head_wt, const float* head_b, int n_classes,
+                 float* logits, hipStream_t stream);
+
+// ---- sepws.hip (shapes checked by cnn.hip's launch_pointwise_ws; false: shape not covered) ----
+void launch_pointwise_res(const float* in, float* out, int rows, const SepLayer& L, hipStream_t stream);
+void launch_pointwise_sep_ws(const float* in, float* out, int64_t rows, const SepLayer& L, hipStream_t stream);
+bool launch_sep_ws_next_dw(const float* in, float* out, int windows, const SepLayer& L, const SepLayer& next, hipStream_t stream);
+
+// ---- l4window.hip ----
+bool launch_l4_window_next_dw(const float* in, float* out, int windows, const SepLayer& L, const SepLayer& next, hipStream_t stream);
+// layer 3's 1x1 convolution + layer 4 + depthwise 5 on the planes launch_stem_reg_planes writes: would it run?
+bool l4_window_planes_supported(const SepLayer& L3, const SepLayer& L4, const SepLayer& L5);
+bool launch_l4_window_planes(const void* planes, const SepLayer& L3, const SepLayer& L4, const SepLayer& L5, float* out,
+                             int windows, hipStream_t stream);
+
+// ---- stem3.hip ----
+void launch_stem4(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
+                  const float* c1_b,
+                  const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);
+
+// ---- stemreg.hip ----
+void launch_stem_reg(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
+                     const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);
+void launch_stem_reg_planes(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
+                            const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);   // planes for launch_l4_window_planes
+
+// ---- stemregf32.hip ----
+void launch_stem_reg_f32(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
+                         const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);
+
+// ---- l4regf32.hip ----
 bool launch_l4_reg_f32(const float* in, float* out, int windows, const SepLayer& L4, const SepLayer& L5, hipStream_t stream);
-bool launch_separable_chip(const float* in, float* out, int windows, const SepLayer* L, int nl, hipStream_t stream,
-                           const SepLayer* next = nullptr, bool planes = false);
-bool tail_supported(const SepLayer& L13, const SepLayer& L14);      // septail.hip: would the two launches below run?
-bool launch_tail_pw13_dw14(const void* in, void* out, int windows, const SepLayer& L13, const SepLayer& L14, hipStream_t stream);   // septail.hip
-bool launch_tail_pw14_pool(const void* in, float* pooled, int windows, const SepLayer& L14, hipStream_t stream);
-bool tail_f32_supported(const SepLayer& L13, const SepLayer& L14);
-// which = 0: pointwise 13 + depthwise 14 (in -> mid); 1: pointwise 14 + pool (mid -> pooled)
-bool launch_tail_f32(const float* in, float* mid, float* pooled, int windows, const SepLayer& L13, const SepLayer& L14, hipStream_t stream,
-                     int which);
-bool launch_separable_chip_f32(const float* in, float* out, int windows, const SepLayer* L, int nl, hipStream_t stream,
-                               const SepLayer* next, bool dw0_done);
-bool launch_separable_mid_f32(const float* in, float* out, int windows, const SepLayer& L5, const SepLayer& L6, const SepLayer& L7,
-                              hipStream_t stream);   // sepchip.hip
+
+// ---- sepmid.hip ----
 bool launch_separable_mid(const float* in, float* out, int windows, const SepLayer& L5, const SepLayer& L6, const SepLayer& L7,
-                          hipStream_t stream);       // sepmid.hip
+                          hipStream_t stream);
 // The split-f16 depthwise-7 output handed from sep_mid_kernel to sep_chip_kernel, per window: [stage 0..7][hi, lo][24 rows
 // (4 oy + ox)][32 channels] f16 (the lo planes are not written in the plain-f16 mode)
 constexpr int kDw7PlaneBytes = 8 * 2 * 24 * 32 * 2;
 bool separable_mid_planes_supported(const SepLayer& L5, const SepLayer& L6, const SepLayer& L7);
 bool launch_separable_mid_planes(const float* in, void* out, int windows, const SepLayer& L5, const SepLayer& L6, const SepLayer& L7,
                                  hipStream_t stream);
-// pointwise 7 on those planes + layers 8-12 + depthwise 13 (sepchip.hip), out = the planes septail.hip reads
+
+// ---- sepmidf32.hip ----
+bool launch_separable_mid_f32(const float* in, float* out, int windows, const SepLayer& L5, const SepLayer& L6, const SepLayer& L7,
+                              hipStream_t stream);
+
+// ---- sepchip.hip ----
+// pointwise 7 on those planes + layers 8-12 + depthwise 13, out = the planes septail.hip reads
 bool separable_chip_pw7_supported(const SepLayer& L7, const SepLayer* L, int nl, const SepLayer& next, int windows);
 bool launch_separable_chip_pw7(const void* in, float* out, int windows, const SepLayer& L7, const SepLayer* L, int nl,
                                const SepLayer& next, hipStream_t stream);
 int launch_separable_run_next_dw(const float* a, float* b, int windows, const SepLayer* L, int max_layers, hipStream_t stream,
                                  bool planes = false);
-bool launch_separable_fused_next_dw(const float* in, float* out, int windows, const SepLayer& L, const SepLayer& next,
-                                    hipStream_t stream);
-// layer 3's 1x1 convolution + layer 4 + depthwise 5 on the planes launch_stem_reg_planes writes (cnn.hip): would it run?
-bool l4_window_planes_supported(const SepLayer& L3, const SepLayer& L4, const SepLayer& L5);
-bool launch_l4_window_planes(const void* planes, const SepLayer& L3, const SepLayer& L4, const SepLayer& L5, float* out,
-                             int windows, hipStream_t stream);
-void launch_stem_reg(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
-                     const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);
-void launch_stem_reg_planes(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
-                            const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);   // planes for launch_l4_window_planes
-void launch_stem_reg_f32(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
-                         const float* c1_b, const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);   // stemregf32.hip
-void launch_stem4(const float* logmel, int patch_step, const WindowMap& map, int w0, int windows, const float* c1_w,
-                  const float* c1_b,
-                  const SepLayer& L2, const SepLayer& L3, float* out, hipStream_t stream);
-void launch_pool_head(const float* act, int windows, const float* head_wt, const float* head_b,
-                      int n_classes, float* emb, float* logits, hipStream_t stream);
-void launch_head(const float* pooled, int windows, const float* head_wt, const float* head_b, int n_classes,
-                 float* logits, hipStream_t stream);
 
-// One Dense layer of an attached head stack (headmlp.hip, include/buzzdetect_head.h)
+// ---- sepchipf32.hip ----
+bool launch_separable_chip_f32(const float* in, float* out, int windows, const SepLayer* L, int nl, hipStream_t stream,
+                               const SepLayer* next, bool dw0_done);
+
+// ---- septail.hip ----
+bool tail_supported(const SepLayer& L13, const SepLayer& L14);      // would the two launches below run?
+bool launch_tail_pw13_dw14(const void* in, void* out, int windows, const SepLayer& L13, const SepLayer& L14, hipStream_t stream);
+bool launch_tail_pw14_pool(const void* in, float* pooled, int windows, const SepLayer& L14, hipStream_t stream);
+bool tail_f32_supported(const SepLayer& L13, const SepLayer& L14);
+// which = 0: pointwise 13 + depthwise 14 (in -> mid); 1: pointwise 14 + pool (mid -> pooled)
+bool launch_tail_f32(const float* in, float* mid, float* pooled, int windows, const SepLayer& L13, const SepLayer& L14, hipStream_t stream,
+                     int which);
+
+// ---- headmlp.hip ----
+// One Dense layer of an attached head stack (include/buzzdetect_head.h)
 struct DenseLayer {
     int k, n;            // inputs, outputs
     int act;             // BD_HEAD_*

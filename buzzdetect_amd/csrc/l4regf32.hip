@@ -14,16 +14,13 @@
 //     the kernel spills and was slower): two per CU as before, 136-139 vs 142-143 us per 938 windows (same box).
 // Arithmetic per element is l4_f32_kernel's, i.e. depthwise_kernel, pointwise_kernel, depthwise_kernel's: bit-identical
 // (tests/test_gpu_parity.py::test_fused_f32_mode_equals_one_kernel_per_op).
-#include "bd_internal.h"
+#include "bd_device.h"
 
 #include <type_traits>
 
 namespace bd {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kH = 24, kW = 16, kC = 128, kKC = 32;
 constexpr int kBandBytes = 6 * 18 * kKC * 4;              // 13824: six input rows x (16 + 2 halo) columns x 32 channels

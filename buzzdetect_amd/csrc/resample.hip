@@ -37,21 +37,15 @@
 // Bound: the matrix pipe (3 K / 16 MFMAs per 1024 outputs: 29 us per 1024-window batch of 48 kHz input at 2.1 GHz) and
 // HBM (16 B read + 4 B written per output for 48 kHz stereo 16-bit: 45 us at 5.6 TB/s) are within a factor of two of
 // each other; DESIGN.md has the measured number.
-#include "bd_internal.h"
+#include "bd_device.h"
 
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 namespace bd {
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kFirWaves = 4;
 constexpr int kFirThreads = 64 * kFirWaves;
@@ -361,8 +355,7 @@ __device__ __forceinline__ void fir_body(const T* __restrict__ in, long long n_i
     // (a native 4-vector, so that both sides are ONE ds_write_b128 / ds_read_b128 per lane: with HIP's float4 struct the
     //  compiler split the reads into ds_read_b32 / ds_read2_b32 at a 16-byte lane stride - 8 lanes per bank, 24 conflict cycles
     //  per instruction, 92 % of the kernel's SQ_LDS_BANK_CONFLICT (round 5, tools/fir_conflicts.sh))
-    typedef float fir_v4 __attribute__((ext_vector_type(4)));
-    fir_v4* const red = reinterpret_cast<fir_v4*>(smem);
+    v4f* const red = reinterpret_cast<v4f*>(smem);
 #pragma unroll
     for (int t = 0; t < MT; ++t)
 #pragma unroll
@@ -370,17 +363,17 @@ __device__ __forceinline__ void fir_body(const T* __restrict__ in, long long n_i
 #if defined(BD_FIR_ABLATE) && BD_FIR_ABLATE == 3      // developer build: partial tiles not written (the sums below read garbage)
             asm volatile("" ::"v"(acc[t][4 * g]), "v"(acc[t][4 * g + 1]), "v"(acc[t][4 * g + 2]), "v"(acc[t][4 * g + 3]));
 #else
-            red[((wave * MT + t) * 4 + g) * 64 + lane] = fir_v4{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
+            red[((wave * MT + t) * 4 + g) * 64 + lane] = v4f{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
 #endif
     __syncthreads();
     const int g = wave;                                    // this wave sums register quad g of every tile
     const int col = lane & 31;
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
-        fir_v4 s = red[((0 * MT + t) * 4 + g) * 64 + lane];
+        v4f s = red[((0 * MT + t) * 4 + g) * 64 + lane];
 #pragma unroll
         for (int w = 1; w < kFirWaves; ++w) {
-            fir_v4 r = red[((w * MT + t) * 4 + g) * 64 + lane];
+            v4f r = red[((w * MT + t) * 4 + g) * 64 + lane];
             asm volatile("" : "+v"(r));                     // (one 16-byte read: not four dword reads the scheduler may spread out)
             s.x += r.x; s.y += r.y; s.z += r.z; s.w += r.w;
         }
@@ -537,13 +530,7 @@ void launch_fir_mfma(const void* in, bool s16, int64_t n_in, int channels, const
     const dim3 grid((unsigned)gx, (unsigned)p.NB);
 #define BD_FIR_LAUNCH_CH(T, KQ, MT, CH)                                                                           \
     do {                                                                                                          \
-        static std::once_flag once_[16];                                                                          \
-        int dev_ = 0;                                                                                             \
-        (void)hipGetDevice(&dev_);                                                                                \
-        std::call_once(once_[dev_ & 15], [] {                                                                     \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fir_mfma_kernel<T, KQ, MT, CH>),             \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                    \
-        });                                                                                                       \
+        allow_dynamic_lds<&fir_mfma_kernel<T, KQ, MT, CH>>(160 * 1024);                                           \
         hipLaunchKernelGGL((fir_mfma_kernel<T, KQ, MT, CH>), grid, dim3(kFirThreads), (size_t)p.lds_bytes, stream, \
                            static_cast<const T*>(in), (long long)n_in, channels, p, out, (long long)n_out,        \
                            (long long)n_chunks);                                                                  \

@@ -26,21 +26,11 @@
 // q = 0..31 in ascending order; which wave owns which column block changes nothing.  Taps that fall outside the map are skipped
 // instead of multiplied by zero: fma(0, w, a) == a for every a but -0.0, and a sum that starts at a float shift is never -0.0
 // unless the shift is (then the result differs in the sign of a zero that the ReLU absorbs).
-#include "bd_internal.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <mutex>
+#include "bd_device.h"
 
 namespace bd {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float kF16MaxChip = 65504.0f;
 
 // LDS image of one stage's A tile: two halves (hi, lo) of [96 rows][32 k] f16 = 64-byte rows, the 16-byte slot of a row
 // XORed with (row >> 2) & 3 (the swizzle of the round 2-5 kernels: the 8 rows a ds_read_b128 lane group touches land in different
@@ -489,13 +479,11 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
             }
         }
     }
-    if (range_flag && !(rmax <= kF16MaxChip)) *range_flag = 1u;
+    range_report(rmax, range_flag);
     if constexpr (TRACE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     CHIP_TS()
 #undef CHIP_TS
 }
-
-constexpr int kMaxDevicesChip = 64;
 
 template <bool PLAIN, bool NDW, bool PLANES = false, bool PW7 = false>
 void launch_chip(const float* in, float* out, const SepLayer* L, int nl, long long M, const float* ndw_w, hipStream_t stream,
@@ -519,40 +507,21 @@ void launch_chip(const float* in, float* out, const SepLayer* L, int nl, long lo
     constexpr int NSLOT = 13;
     constexpr int lds = NSLOT * kChipSlotBytes;
     static_assert(lds <= 160 * 1024, "the ring must fit the CU's LDS");
-    static std::once_flag once[kMaxDevicesChip];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::call_once(once[dev & (kMaxDevicesChip - 1)], [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_chip_kernel<PLAIN, NSLOT, false, NDW, PLANES, PW7>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    });
+    allow_dynamic_lds<&sep_chip_kernel<PLAIN, NSLOT, false, NDW, PLANES, PW7>>(lds);
     const long long tiles = (M + 95) / 96;
     int tune = 0;
 #ifdef BD_KERNEL_TRACE      // developer build only: BD_CHIP_TUNE = policy under test; BD_WS_TRACE=7 stamps workgroup 0
     if (const char* tn = getenv("BD_CHIP_TUNE")) tune = atoi(tn);
-    const char* tr = getenv("BD_WS_TRACE");
-    if (tr && tr[0] == '7') {
-        static unsigned long long* dbg = nullptr;
-        static int shots = 0;
-        if (!dbg) (void)hipMalloc(&dbg, 128 * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_chip_kernel<PLAIN, NSLOT, true, NDW, PLANES, PW7>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipMemsetAsync(dbg, 0, 128 * 8, stream);
-        hipLaunchKernelGGL((sep_chip_kernel<PLAIN, NSLOT, true, NDW, PLANES, PW7>), dim3((unsigned)tiles), dim3(512), lds, stream, ch, in, out, nl,
-                           M, L[0].range_flag, dbg, tune);
-        (void)hipStreamSynchronize(stream);
-        unsigned long long h[128];
-        (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-        if (++shots == 8)
-            for (int w = 0; w < 2; ++w) {
-                fprintf(stderr, "[trace] on-chip run of %d layers%s, wave %d: cycles between stamps (start | %s | per layer: B1, stages 0-2, B2, pend, "
-                                "B3, stages 3-15, [dw j0, dw j1, B4] | stores):", nl, PW7 ? " + pointwise 7" : "", w ? 5 : 0,
-                        PW7 ? "DMA, B1, -, -, -, stages 0-7, dw j0, dw j1, B4" : "dw0 j0 j1");
-                for (int i = 1; i < 64 && h[w * 64 + i]; ++i) fprintf(stderr, " %llu", h[w * 64 + i] - h[w * 64 + i - 1]);
-                fprintf(stderr, "\n");
-            }
+    if (traced_launch(
+            '7', &sep_chip_kernel<PLAIN, NSLOT, true, NDW, PLANES, PW7>, lds, stream, 64, 5, nullptr,
+            [&](unsigned long long* dbg) {
+                hipLaunchKernelGGL((sep_chip_kernel<PLAIN, NSLOT, true, NDW, PLANES, PW7>), dim3((unsigned)tiles), dim3(512), lds, stream, ch, in, out, nl,
+                                   M, L[0].range_flag, dbg, tune);
+            },
+            "on-chip run, wave %d, %d layers%s: cycles between stamps (start | %s | per layer: B1, stages 0-2, B2, pend, B3, stages 3-15, "
+            "[dw j0, dw j1, B4] | stores):",
+            nl, PW7 ? " + pointwise 7" : "", PW7 ? "DMA, B1, -, -, -, stages 0-7, dw j0, dw j1, B4" : "dw0 j0 j1"))
         return;
-    }
 #endif
     hipLaunchKernelGGL((sep_chip_kernel<PLAIN, NSLOT, false, NDW, PLANES, PW7>), dim3((unsigned)tiles), dim3(512), lds, stream, ch, in, out, nl, M,
                        L[0].range_flag, (unsigned long long*)nullptr, tune);
@@ -562,13 +531,13 @@ void launch_chip(const float* in, float* out, const SepLayer* L, int nl, long lo
 
 // A run of stride-1 512 -> 512 layers on the 6 x 4 map with the tiles between its layers kept on the CU: reads `in`, writes
 // `out`.  They may be the same buffer: a workgroup has read all rows of its tile before it writes any.  The caller has
-// checked the shapes (launch_separable_run_next_dw).  With `next` (the stride-2 layer behind the run) the run's output is not written:
+// checked the shapes (launch_separable_run_next_dw below).  With `next` (the stride-2 layer behind the run) the run's output is not written:
 // next's depthwise is applied in the epilogue and out = [windows][3][2][512] (then `out` must not be `in`: the tiles' rows
 // differ).  False (nothing launched) when a layer's shift table does not follow its taps (the kernel reads both through
 // one [10][512] resource; engine.hip lays dw_b16 behind dw_w16).
 // planes (with next): the output leaves as f16 hi / lo planes [windows * 6][512] (hi at out, lo behind it), what septail.hip reads.
-bool launch_separable_chip(const float* in, float* out, int windows, const SepLayer* L, int nl, hipStream_t stream,
-                           const SepLayer* next, bool planes) {
+static bool launch_separable_chip(const float* in, float* out, int windows, const SepLayer* L, int nl, hipStream_t stream,
+                                  const SepLayer* next, bool planes) {
     if (planes && !next) return false;
     if (nl < 1 || nl > kChipMaxLayers) return false;
     for (int i = 0; i < nl; ++i)
@@ -589,6 +558,24 @@ bool launch_separable_chip(const float* in, float* out, int windows, const SepLa
         else launch_chip<false, false>(in, out, L, nl, M, nw, stream);
     }
     return true;
+}
+
+// The run of stride-1 512 -> 512 layers on the 6 x 4 map (layers 8-11) extended by the layer that closes it - the stride-1
+// 512 -> 512 layer whose successor is a stride-2 one (layer 12) - with that successor's depthwise in the epilogue: layers 8-12 +
+// depthwise 13 as ONE launch of the on-chip kernel, a -> b = [windows][3][2][512] (planes: as f16 hi / lo planes,
+// what septail.hip reads).  Returns the number of layers of L it ran (5) or 0 (the caller goes on layer by layer).
+int launch_separable_run_next_dw(const float* a, float* b, int windows, const SepLayer* L, int max_layers, hipStream_t stream,
+                                 bool planes) {
+    int n = 0;
+    while (n < 5 && n + 1 < max_layers) {
+        const SepLayer& l = L[n];
+        if (l.stride != 1 || l.cin != 512 || l.cout != 512 || l.h_out != 6 || l.w_out != 4 || l.pw_mode != L[0].pw_mode) return 0;
+        ++n;
+        if (L[n].stride != 1) break;
+    }
+    if (n < 2 || n > 5 || n >= max_layers || L[n].stride != 2 || L[n].cin != 512 || windows <= 0 || (long long)windows * 24 >= (1LL << 31))
+        return 0;
+    return launch_separable_chip(a, b, windows, L, n, stream, &L[n], planes) ? n : 0;
 }
 
 // Pointwise 7 (L7) on the depthwise-7 planes sep_mid_kernel<.., DW7OUT> writes (kDw7PlaneBytes per window), then the run L[0 ..

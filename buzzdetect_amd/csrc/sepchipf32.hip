@@ -19,17 +19,11 @@
 // with fmaf, ReLU; per accumulator the k pairs {8 s + j, 8 s + 4 + j}, j = 0..3, of super-step s = 0..63 in ascending order
 // (pointwise_kernel's operand map); epilogue acc + shift, ReLU.  Taps outside the map are skipped (sepchip.hip on why that is
 // the multiplied zero's result).  tests/test_gpu_parity.py::test_fused_f32_mode_equals_one_kernel_per_op covers it.
-#include "bd_internal.h"
-
-#include <mutex>
+#include "bd_device.h"
 
 namespace bd {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kF32RowBytes = 128;
 constexpr int kF32SlotBytes = 97 * kF32RowBytes;       // 12 416
@@ -324,13 +318,7 @@ void launch_chip_f32(const float* in, float* out, const SepLayer* L, int nl, lon
     constexpr int NSLOT = 13;
     constexpr int lds = NSLOT * kF32SlotBytes;
     static_assert(lds <= 160 * 1024, "the ring must fit the CU's LDS");
-    static std::once_flag once[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::call_once(once[dev & 63], [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_chip_f32_kernel<NSLOT, NDW, DW0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    });
+    allow_dynamic_lds<&sep_chip_f32_kernel<NSLOT, NDW, DW0>>(lds);
     const long long tiles = (M + 95) / 96;
     hipLaunchKernelGGL((sep_chip_f32_kernel<NSLOT, NDW, DW0>), dim3((unsigned)tiles), dim3(512), lds, stream, ch, in, out, nl, M);
 }

@@ -23,22 +23,14 @@
 // Arithmetic per element is that of the kernels it replaces (pw_res_kernel, sep_ws_kernel<NDW = 1>): products lo*hi, hi*lo,
 // hi*hi per k16 step in ascending order, relu(fma(acc, u, b)), depthwise = shift then taps in row-major order with fmaf, the
 // range guard's maximum over everything that is split.  Taps outside the map are skipped or multiply a zero (sepchip.hip).
-#include "bd_internal.h"
+#include "bd_device.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <mutex>
 #include <type_traits>
 
 namespace bd {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float kF16MaxMid = 65504.0f;
 constexpr int kHalfA = 97 * 64;                 // one f16 half of a 96-row stage (rows 48.. one row further)
 constexpr int kSlotA = 2 * kHalfA;              // 12416
 constexpr int kHalf7 = 48 * 64;                 // layer 7's A operand: the 24 rows of TWO windows per stage
@@ -88,7 +80,6 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
     const int ra0 = frow * 64 + ((fh ^ ((frow >> 2) & 3)) << 4);
     const int ra1 = ra0 + 2048 + (frow >= 16 ? 64 : 0);
     const unsigned lane16 = lane * 16, c4 = frow * 4;
-
 
 #define MID_PUT(BASE, RL, PK)                                                                             \
     {                                                                                                     \
@@ -345,7 +336,6 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
                 // bytes per lane.  (A 16-byte store whose data registers are overwritten two vector instructions later has been
                 // seen to store the new values - DESIGN.md 10: the store and three wait states behind it are one asm statement)
                 typedef __attribute__((address_space(1))) char* gchar;
-                typedef float v4f __attribute__((ext_vector_type(4)));
                 asm volatile("" ::: "memory");
                 const gchar dst = (gchar)Y + (size_t)win * kDw7PlaneBytes + wc * kStage7 + lane * 16;
 #pragma unroll
@@ -437,7 +427,7 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
             layer7(std::integral_constant<int, 1>{}, win);
         }
     }
-    if (range_flag && !(rmax <= kF16MaxMid)) *range_flag = 1u;
+    range_report(rmax, range_flag);
 #undef MID_TS
 #undef MID_PUT
 #undef MID_SPLIT
@@ -461,35 +451,18 @@ void launch_mid(const float* in, float* out, int windows, const SepLayer& L5, co
     a.u7 = L7.pw_u; a.b7 = L7.pw_b;
     a.dw6 = dw_w_of(L6);
     a.dw7 = dw_w_of(L7);
-    static std::once_flag once[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::call_once(once[dev & 63], [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_mid_kernel<PLAIN, false, DW7OUT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    });
+    allow_dynamic_lds<&sep_mid_kernel<PLAIN, false, DW7OUT>>(lds);
     int grid = cu_count();
     if (grid > windows) grid = windows;
 #ifdef BD_KERNEL_TRACE      // developer build only: BD_WS_TRACE=8 stamps the phases of workgroup 0 (waves 0 and 5)
-    const char* tr = getenv("BD_WS_TRACE");
-    if (tr && tr[0] == '8') {
-        static unsigned long long* dbg = nullptr;
-        static int shots = 0;
-        if (!dbg) (void)hipMalloc(&dbg, 128 * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_mid_kernel<PLAIN, true, DW7OUT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipMemsetAsync(dbg, 0, 128 * 8, stream);
-        hipLaunchKernelGGL((sep_mid_kernel<PLAIN, true, DW7OUT>), dim3(grid), dim3(512), lds, stream, a, in, out, windows, L5.range_flag, dbg);
-        (void)hipStreamSynchronize(stream);
-        unsigned long long h[128];
-        (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-        if (++shots == 8)
-            for (int w = 0; w < 2; ++w) {
-                fprintf(stderr, "[trace] mid run, wave %d: cycles between stamps (per window: A5+B1, K5, dw6+Bx, publish+B2, K6, %s):", w ? 5 : 0,
-                        DW7OUT ? "dw7 + its planes stored" : "dw7+B3; per pair: K7, stores");
-                for (int i = 1; i < 64 && h[w * 64 + i]; ++i) fprintf(stderr, " %llu", h[w * 64 + i] - h[w * 64 + i - 1]);
-                fprintf(stderr, "\n");
-            }
+    if (traced_launch(
+            '8', &sep_mid_kernel<PLAIN, true, DW7OUT>, lds, stream, 64, 5, nullptr,
+            [&](unsigned long long* dbg) {
+                hipLaunchKernelGGL((sep_mid_kernel<PLAIN, true, DW7OUT>), dim3(grid), dim3(512), lds, stream, a, in, out, windows, L5.range_flag, dbg);
+            },
+            "mid run, wave %d: cycles between stamps (per window: A5+B1, K5, dw6+Bx, publish+B2, K6, %s):",
+            DW7OUT ? "dw7 + its planes stored" : "dw7+B3; per pair: K7, stores"))
         return;
-    }
 #endif
     hipLaunchKernelGGL((sep_mid_kernel<PLAIN, false, DW7OUT>), dim3(grid), dim3(512), lds, stream, a, in, out, windows, L5.range_flag,
                        (unsigned long long*)nullptr);

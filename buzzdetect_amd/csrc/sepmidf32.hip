@@ -10,18 +10,13 @@
 // global load per column tile from the fragment-ordered f32 weights (SepLayer::pw_ffrag), then four matrix instructions per
 // (row tile, column tile).  Arithmetic is depthwise_kernel + pointwise_kernel's bit for bit (sepchipf32.hip);
 // tests/test_gpu_parity.py::test_fused_f32_mode_equals_one_kernel_per_op covers it.
-#include "bd_internal.h"
+#include "bd_device.h"
 
-#include <mutex>
 #include <type_traits>
 
 namespace bd {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kRowB = 128;                      // a stage row: 32 k as f32
 constexpr int kSlotA = 97 * kRowB;              // 12416: a 96-row stage (rows 48.. one row further)
@@ -315,12 +310,7 @@ bool launch_separable_mid_f32(const float* in, float* out, int windows, const Se
     a.b5 = L5.pw_b; a.b6 = L6.pw_b; a.b7 = L7.pw_b;
     a.dw6 = L6.dw_w;
     a.dw7 = L7.dw_w;
-    static std::once_flag once[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::call_once(once[dev & 63], [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sep_mid_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMidF32Lds);
-    });
+    allow_dynamic_lds<&sep_mid_f32_kernel>(kMidF32Lds);
     int grid = cu_count();
     if (grid > windows) grid = windows;
     hipLaunchKernelGGL(sep_mid_f32_kernel, dim3(grid), dim3(512), kMidF32Lds, stream, a, in, out, windows);

@@ -29,22 +29,14 @@
 // depthwise = shift, then the taps inside the map in row-major order with fmaf, ReLU, the range guard's maximum, the split;
 // the pool = the six positions summed in order, divided by 6.  (Taps outside the map are skipped: sepchip.hip on why that is
 // the zero-multiplying tap's result.)
-#include "bd_internal.h"
+#include "bd_device.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <mutex>
 #include <type_traits>
 
 namespace bd {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float kF16MaxTail = 65504.0f;
 constexpr int kTailN = 1024;                   // output channels of both layers
 constexpr int kTailPlane = 96 * 128;           // one f16 half of a stage: 96 rows x 64 input channels
 constexpr int kTailStage = 2 * kTailPlane;     // 24 576
@@ -267,7 +259,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const float six = 6.0f;
             sx /= six;
             sy /= six;
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
             __builtin_amdgcn_raw_buffer_store_b64(u32x2{__builtin_bit_cast(unsigned, sx), __builtin_bit_cast(unsigned, sy)}, pr, po, w * N * 4, 0);
         }
     } else {
@@ -303,7 +294,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     __builtin_amdgcn_raw_buffer_store_b32(hi2, ohr, oo, so, 0);
                     if constexpr (!PLAIN) __builtin_amdgcn_raw_buffer_store_b32(lo2, olr, oo, so, 0);
                 }
-        if (range_flag && !(rmax <= kF16MaxTail)) *range_flag = 1u;
+        range_report(rmax, range_flag);
     }
     TAIL_TS()
     if constexpr (TRACE) {
@@ -336,7 +327,6 @@ struct TailArgsF32 {
 template <int K, int EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void tail_gemm_f32_kernel(const TailArgsF32 a, int M, int windows) {
     extern __shared__ __attribute__((aligned(16))) char sm[];
-    typedef float v4f __attribute__((ext_vector_type(4)));
     constexpr int N = kTailN, NST = K / 64, KS = K / 8;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wc = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -463,7 +453,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const v2f y = v2f{acc[n >> 4][0][n & 15], acc[n >> 4][1][n & 15]} + b2;
         yv[n] = v2f{fmaxf(y.x, 0.0f), fmaxf(y.y, 0.0f)};
     }
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     if constexpr (EPI == 1) {
         const __amdgpu_buffer_rsrc_t pr = TAIL_RSRC(a.pooled, (unsigned)windows * N * 4);
         const unsigned po = (unsigned)((m0 / 6 + 8 * fh) * N + ch0) * 4;
@@ -507,12 +496,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 template <int K, int EPI>
 void launch_tail_f32(const TailArgsF32& a, int windows, hipStream_t stream) {
-    static std::once_flag once[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::call_once(once[dev & 63], [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_gemm_f32_kernel<K, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, kTailLds);
-    });
+    allow_dynamic_lds<&tail_gemm_f32_kernel<K, EPI>>(kTailLds);
     const int M = windows * 6;
     const int nrt4 = ((M + 95) / 96 + 3) / 4 * 4;
     hipLaunchKernelGGL((tail_gemm_f32_kernel<K, EPI>), dim3(4 * nrt4), dim3(256), kTailLds, stream, a, M, windows);
@@ -520,36 +504,18 @@ void launch_tail_f32(const TailArgsF32& a, int windows, hipStream_t stream) {
 
 template <int K, int EPI, bool PLAIN>
 void launch_tail(const TailArgs& a, int windows, unsigned* range_flag, hipStream_t stream) {
-    static std::once_flag once[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::call_once(once[dev & 63], [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_gemm_kernel<K, EPI, PLAIN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kTailLds);
-    });
+    allow_dynamic_lds<&tail_gemm_kernel<K, EPI, PLAIN>>(kTailLds);
     const int M = windows * 6;
     const int nrt4 = ((M + 95) / 96 + 3) / 4 * 4;      // row tiles, rounded up to the four XCD pairs (workgroups past M leave at once)
 #ifdef BD_KERNEL_TRACE      // developer build only: BD_WS_TRACE=9 stamps wave 0 of workgroups 0 and 101
-    const char* tr = getenv("BD_WS_TRACE");
-    if (tr && tr[0] == '9') {
-        static unsigned long long* dbg = nullptr;
-        static int shots[2] = {0, 0};
-        if (!dbg) (void)hipMalloc(&dbg, 64 * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_gemm_kernel<K, EPI, PLAIN, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kTailLds);
-        (void)hipMemsetAsync(dbg, 0, 64 * 8, stream);
-        hipLaunchKernelGGL((tail_gemm_kernel<K, EPI, PLAIN, true>), dim3(4 * nrt4), dim3(256), kTailLds, stream, a, M, windows, range_flag, dbg);
-        (void)hipStreamSynchronize(stream);
-        unsigned long long h[64];
-        (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-        if (++shots[EPI] == 8)
-            for (int w = 0; w < 2; ++w) {
-                fprintf(stderr, "[trace] tail K = %d, workgroup %d: cycles between stamps (prologue | one per stage | epilogue | stores land):", K,
-                        w ? 101 : 0);
-                for (int i = 1; i < 32 && h[w * 32 + i]; ++i) fprintf(stderr, " %llu", h[w * 32 + i] - h[w * 32 + i - 1]);
-                fprintf(stderr, "\n");
-                if (!w) fprintf(stderr, "[trace] ... workgroup 0 lived %llu ticks of the 100 MHz clock\n", h[31] - h[30]);
-            }
+    bool printed = false;
+    if (const unsigned long long* h = traced_launch(
+            '9', &tail_gemm_kernel<K, EPI, PLAIN, true>, kTailLds, stream, 32, 101, &printed,
+            [&](unsigned long long* dbg) {
+                hipLaunchKernelGGL((tail_gemm_kernel<K, EPI, PLAIN, true>), dim3(4 * nrt4), dim3(256), kTailLds, stream, a, M, windows, range_flag, dbg);
+            },
+            "tail, workgroup %d, K = %d: cycles between stamps (prologue | one per stage | epilogue | stores land):", K)) {
+        if (printed) fprintf(stderr, "[trace] ... workgroup 0 lived %llu ticks of the 100 MHz clock\n", h[31] - h[30]);
         return;
     }
 #endif

@@ -30,38 +30,13 @@
 //     moves instead of 72 v_fma_f32 per tile and lane); the 1x1 epilogue of layer 2 is packed the same way.  Arithmetic per element is stem3_kernel's, i.e. conv1_kernel / depthwise_kernel /
 // pointwise_f16x3_kernel's (taps in row-major order with fmaf, zeros outside the map multiplied, products lo*hi, hi*lo, hi*hi per
 // k16 step): bit-identical (tests/test_gpu_parity.py::test_fused_stem_is_bit_identical_to_unfused).
-#include "bd_internal.h"
+#include "bd_device.h"
 
 #include <type_traits>
 
 namespace bd {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-constexpr float kF16MaxReg = 65504.0f;
-
-__device__ __forceinline__ int rg_swz64(int row, int slot) { return row * 64 + ((slot ^ ((row >> 2) & 3)) << 4); }
-__device__ __forceinline__ float rg_range(float m, v4f v) {
-    return fmaxf(fmaxf(m, fabsf(v.x)), fmaxf(fmaxf(fabsf(v.y), fabsf(v.z)), fabsf(v.w)));
-}
-// a = hi + lo, hi = f16(a), lo = f16(a - hi): cnn.hip's split_f16 (one v_fma_mix per low half)
-__device__ __forceinline__ void rg_split(v4f a, f16x4& hi, f16x4& lo) {
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-    const f16x2 h0 = {(_Float16)a.x, (_Float16)a.y}, h1 = {(_Float16)a.z, (_Float16)a.w};
-    f16x2 l0, l1;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(h0), "v"(a.x));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l0) : "v"(h0), "v"(a.y));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(h1), "v"(a.z));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l1) : "v"(h1), "v"(a.w));
-    hi[0] = h0[0]; hi[1] = h0[1]; hi[2] = h1[0]; hi[3] = h1[1];
-    lo[0] = l0[0]; lo[1] = l0[1]; lo[2] = l1[0]; lo[3] = l1[1];
-}
 
 // ---- LDS map (bytes): 53 248, three workgroups per CU ----
 constexpr int OFF_C1 = 0;                        // conv1 band [6][34][32] f32
@@ -240,11 +215,11 @@ __global__ __launch_bounds__(256, 3) void stem_reg_kernel(const float* __restric
                 acc.y = fmaxf(acc.y, 0.0f);
                 acc.z = fmaxf(acc.z, 0.0f);
                 acc.w = fmaxf(acc.w, 0.0f);
-                rmax = rg_range(rmax, acc);
+                rmax = range_of(rmax, acc);
                 f16x4 hi, lo;
-                rg_split(acc, hi, lo);
+                split_f16(acc, hi, lo);
                 const int row = rbase + 32 * (r & 1) + 4 * (r >> 1);
-                const int off = rg_swz64(row, c4 >> 1) + (c4 & 1) * 8;
+                const int off = swz64(row, c4 >> 1) + (c4 & 1) * 8;
                 *reinterpret_cast<f16x4*>(s_ah + off) = hi;
                 *reinterpret_cast<f16x4*>(s_al + off) = lo;
 #pragma unroll
@@ -272,7 +247,7 @@ __global__ __launch_bounds__(256, 3) void stem_reg_kernel(const float* __restric
             for (int r = 0; r < 16; ++r) acc2[t][r] = 0.0f;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const int off = rg_swz64((2 * g + t) * 32 + frow, 2 * s2 + fh);
+                const int off = swz64((2 * g + t) * 32 + frow, 2 * s2 + fh);
                 const f16x8 ah = *reinterpret_cast<const f16x8*>(s_ah + off);
                 const f16x8 al = *reinterpret_cast<const f16x8*>(s_al + off);
                 if constexpr (!PLAIN) {
@@ -403,8 +378,8 @@ __global__ __launch_bounds__(256, 3) void stem_reg_kernel(const float* __restric
                                  "v_fma_mixhi_f16 %1, %0, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
                                  "v_max3_f32 %2, %2, %3, %4"
                                  : "=&v"(pkh), "=&v"(pkl), "+v"(rmax) : "v"(v0), "v"(v1));
-                    const int off0 = wc * (32 * 64) + rg_swz64(fh * 16 + 8 * g + 2 * k, frow >> 3) + (frow & 7) * 2;
-                    const int off1 = wc * (32 * 64) + rg_swz64(fh * 16 + 8 * g + 2 * k + 1, frow >> 3) + (frow & 7) * 2;
+                    const int off0 = wc * (32 * 64) + swz64(fh * 16 + 8 * g + 2 * k, frow >> 3) + (frow & 7) * 2;
+                    const int off1 = wc * (32 * 64) + swz64(fh * 16 + 8 * g + 2 * k + 1, frow >> 3) + (frow & 7) * 2;
                     *reinterpret_cast<unsigned short*>(smem + OFF_A3H + off0) = (unsigned short)pkh;
                     *reinterpret_cast<unsigned short*>(smem + OFF_A3H + off1) = (unsigned short)(pkh >> 16);
                     *reinterpret_cast<unsigned short*>(smem + OFF_A3L + off0) = (unsigned short)pkl;
@@ -443,7 +418,7 @@ __global__ __launch_bounds__(256, 3) void stem_reg_kernel(const float* __restric
                 for (int r = 0; r < 16; ++r) acc3[r] = 0.0f;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int off = (q >> 1) * 32 * 64 + rg_swz64(frow, 2 * (q & 1) + fh);
+                    const int off = (q >> 1) * 32 * 64 + swz64(frow, 2 * (q & 1) + fh);
                     const f16x8 ah = *reinterpret_cast<const f16x8*>(smem + OFF_A3H + off);
                     const f16x8 al = *reinterpret_cast<const f16x8*>(smem + OFF_A3L + off);
                     if constexpr (!PLAIN) {
@@ -465,7 +440,7 @@ __global__ __launch_bounds__(256, 3) void stem_reg_kernel(const float* __restric
             //  layer-2 A tile - and the halo words are one / three barriers away)
         }
     }
-    if (range_flag && !(rmax <= kF16MaxReg)) *range_flag = 1u;
+    range_report(rmax, range_flag);
 }
 
 }  // namespace

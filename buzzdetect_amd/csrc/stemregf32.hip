@@ -8,17 +8,13 @@
 // Arithmetic per element is stem3_f32_kernel's, i.e. conv1_kernel / depthwise_kernel / pointwise_kernel's (k pairs {8 s + j,
 // 8 s + 4 + j}, j = 0..3, of super-step s in ascending order; epilogue acc + shift, ReLU): bit-identical
 // (tests/test_gpu_parity.py::test_fused_f32_mode_equals_one_kernel_per_op).
-#include "bd_internal.h"
+#include "bd_device.h"
 
 #include <type_traits>
 
 namespace bd {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 // ---- LDS map (bytes): 53 248, three workgroups per CU ----
 constexpr int OFF_C1 = 0;                        // conv1 band [6][34][32] f32

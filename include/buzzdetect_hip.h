@@ -239,7 +239,7 @@ BD_API int bd_stage_tap(bd_handle h, const float* pcm_dev, int64_t n_samples, in
 
 /* Tuning / test hooks for the pointwise (1x1 convolution) GEMM, yamnet.py:64-70 after BN folding:
    c[m][n] = relu(sum_k a[m][k] * wt[n][k] + bias[n]); k % 32 == 0, n % 64 == 0.
-   variant 0 = the library's choice for the shape; 1..8 = explicit tile shapes (see cnn.hip). */
+   variant 0 = the library's choice for the shape; 1..8 = explicit tile shapes (see launch_pointwise_variant in cnn.hip). */
 BD_API int bd_debug_pointwise(const float* a_dev, const float* wt_dev, const float* bias_dev, float* c_dev,
                               int64_t m, int32_t n, int32_t k, int32_t variant, void* stream);
 /* Per layer, in the f16 modes: 0 = the library's choice (layers 5 and 7: weights in registers, pw_res_kernel; 128+ input
