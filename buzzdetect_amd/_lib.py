@@ -231,6 +231,35 @@ TRAIN_PROTOTYPES = {
     "bd_trainer_workspace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
 }
 
+BANK_ABI_VERSION = 1
+BANK_GROUP_COLUMNS = 64
+BANK_MAX_MEMBERS = 4096
+BANK_MAX_WORKSPACE_BYTES = 1 << 31
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_bank.h
+BANK_PROTOTYPES = {
+    "bd_bank_abi_version": (C.c_int, []),
+    "bd_bank_create": (C.c_int, [C.c_int, C.POINTER(bd_head_layer), C.c_int32, C.c_int32, C.POINTER(bd_train_optimizer),
+                                 C.c_int32, C.POINTER(C.c_void_p)]),
+    "bd_bank_destroy": (C.c_int, [C.c_void_p]),
+    "bd_bank_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                               C.c_void_p]),
+    "bd_bank_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                               C.c_void_p, C.c_void_p]),
+    "bd_bank_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_bank_set_learning_rate": (C.c_int, [C.c_void_p, C.c_int32, C.c_float]),
+    "bd_bank_set_weight_decay": (C.c_int, [C.c_void_p, C.c_int32, C.c_float]),
+    "bd_bank_set_frozen": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "bd_bank_snapshot": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_bank_restore": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_bank_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_bank_gradients": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_bank_mean_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_bank_workspace_floats": (C.c_int64, [C.c_void_p]),
+    "bd_bank_workspace_fill": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "bd_bank_workspace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -263,7 +292,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             raise RuntimeError(f"{path} is older than its sources and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
-            + list(HEAD_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()):
+            + list(HEAD_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
+            + list(BANK_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -279,6 +309,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: any-ratio ABI version {lib.bd_anyrate_abi_version()} != {ANYRATE_ABI_VERSION}; rebuild")
     if lib.bd_train_abi_version() != TRAIN_ABI_VERSION:
         raise RuntimeError(f"{path}: trainer ABI version {lib.bd_train_abi_version()} != {TRAIN_ABI_VERSION}; rebuild")
+    if lib.bd_bank_abi_version() != BANK_ABI_VERSION:
+        raise RuntimeError(f"{path}: head-bank ABI version {lib.bd_bank_abi_version()} != {BANK_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

@@ -1,4 +1,5 @@
-"""Fit a classifier head on the GPU and save it as a model directory (include/buzzdetect_train.h, csrc/headtrain.hip).
+"""Fit a classifier head on the GPU and save it as a model directory (include/buzzdetect_train.h, csrc/headtrain.hip;
+many heads at once: include/buzzdetect_bank.h, csrc/headbank.hip).
 
 The bring-your-own-labels loop without a foreign toolchain:
 
@@ -26,6 +27,13 @@ early_stopping={"patience": 3}, validation=(emb_val, labels_val))``.
   the SGD or Adam update.  Order within an epoch: the learning rate of the epoch is set, the steps run, the validation loss
   is computed, the epoch's one host read takes place, and - with ``early_stopping`` - that read decides: an improvement
   snapshots the parameters on the device, ``patience`` epochs without one end the fit, and the snapshot is what comes back.
+
+Many heads in one pass (include/buzzdetect_bank.h, csrc/headbank.hip): ``fit_heads(emb, labels, classes, members)`` fits a list
+of one-layer heads that differ only in rate, decay, weights and stopping - every member bit for bit the ``fit_head`` call it
+stands for, each step's rows gathered once for all of them - and ``cross_validate_head(emb, labels, classes, folds=5,
+groups=recordings, grid=[...])`` builds grouped, stratified folds, fits every (fold, grid entry) that way and returns
+out-of-fold logits, ``metrics(class_name)`` for an honest threshold, and the grid entry to refit on all rows.  A fold is row
+weights: held-out rows weigh 0 while fitting and are the only ones that weigh in ``val_loss``.
 
 Out of scope: dropout, penalties added to the loss, a per-class ``pos_weight`` for the binary loss, focal loss and label
 smoothing, resuming a fit from a snapshot, ``.keras`` / ``.h5`` output, multi-GPU training, and training anything below the
@@ -213,6 +221,161 @@ class Trainer:
     def workspace(self) -> np.ndarray:
         out = np.empty(_lib.check(self._lib.bd_trainer_workspace_floats(self._handle)), dtype=np.float32)
         _lib.check(self._lib.bd_trainer_workspace_read(self._handle, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+
+class TrainerBank:
+    """``bd_bank_*`` on torch tensors (include/buzzdetect_bank.h): ``members`` = [(kernel [1024, C], bias [C]), ...] are the
+    initial values of M one-layer heads that share every step's rows, targets and batch order and keep their own parameters,
+    slots, rate, decay, row weights, running loss, snapshot and frozen flag.  Member m is, bit for bit, the ``Trainer`` that
+    got the same calls with row m of the weights."""
+
+    def __init__(self, members, loss: str = "categorical", optimizer: str = "adam", learning_rate: float = 1e-3,
+                 beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, max_batch: int = 256,
+                 device: Optional[int] = None):
+        import torch
+        self._handle = C.c_void_p()
+        self._lib = _lib.load()
+        if loss not in _lib.TRAIN_LOSSES:
+            raise ValueError(f'loss must be one of {sorted(_lib.TRAIN_LOSSES)}, not "{loss}"')
+        if optimizer not in _lib.TRAIN_OPTIMIZERS:
+            raise ValueError(f'optimizer must be one of {sorted(_lib.TRAIN_OPTIMIZERS)}, not "{optimizer}"')
+        members = list(members)
+        if not members:
+            raise ValueError("a bank needs at least one member")
+        if not torch.cuda.is_available():
+            raise RuntimeError("buzzdetect_amd: no HIP device visible to PyTorch; the trainer has no CPU path")
+        self.device_index = torch.cuda.current_device() if device is None else int(device)
+        self.device = torch.device("cuda", self.device_index)
+        self.loss = loss
+        self.max_batch = int(max_batch)
+        self.n_members = len(members)
+        arr = (_lib.bd_head_layer * len(members))()
+        keep = []
+        for i, member in enumerate(members):
+            k = np.ascontiguousarray(member[0], dtype=np.float32)
+            b = np.ascontiguousarray(member[1], dtype=np.float32)
+            if k.ndim != 2 or b.shape != (k.shape[1],):
+                raise ValueError(f"member {i}: a kernel [1024, C] and a bias [C], not {k.shape} and {b.shape}")
+            keep += [k, b]
+            arr[i].kernel = k.ctypes.data_as(C.POINTER(C.c_float))
+            arr[i].bias = b.ctypes.data_as(C.POINTER(C.c_float))
+            arr[i].n_in, arr[i].n_out = k.shape
+            arr[i].activation = _lib.HEAD_ACTIVATIONS["linear"]
+        self.n_out = int(arr[0].n_out)
+        opt = _lib.bd_train_optimizer(_lib.TRAIN_OPTIMIZERS[optimizer], learning_rate, beta_1, beta_2, epsilon, 0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.bd_bank_create(self.device_index, arr, len(members), _lib.TRAIN_LOSSES[loss], C.byref(opt),
+                                                self.max_batch, C.byref(self._handle)))
+
+    def close(self) -> None:
+        if getattr(self, "_handle", None) is not None and self._handle.value:
+            self._lib.bd_bank_destroy(self._handle)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _batch(self, X, rows, targets, B, weights=None):
+        import torch
+        if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.device != self.device:
+            raise ValueError("X must be a float32 [N, >= 1024] matrix on the bank's device with unit column stride")
+        if rows is not None and (rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() < B):
+            raise ValueError("rows must be a contiguous int32 tensor of at least B entries")
+        if rows is None and X.shape[0] < B:
+            raise ValueError("X has fewer than B rows")
+        if targets is not None:
+            want = torch.float32 if self.loss == "binary" else torch.int32
+            if targets.dtype != want or not targets.is_contiguous() or targets.numel() < B * (self.n_out if self.loss == "binary" else 1):
+                raise ValueError(f"targets must be a contiguous {want} tensor covering the batch")
+        w, ldw = None, 0
+        if weights is not None:
+            if weights.dtype != torch.float32 or weights.dim() != 2 or weights.shape[0] != self.n_members or weights.shape[1] < B \
+                    or weights.stride(1) != 1 or weights.device != self.device or (self.n_members > 1 and weights.stride(0) < B):
+                raise ValueError("weights must be a float32 [members, >= B] matrix on the bank's device with unit column stride")
+            w, ldw = C.c_void_p(weights.data_ptr()), max(int(weights.stride(0)), int(B))
+        return (C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(rows.data_ptr()) if rows is not None else None,
+                C.c_void_p(targets.data_ptr()) if targets is not None else None, w, ldw, int(B))
+
+    def step(self, X, rows, targets, B: int, weights=None) -> None:
+        """One optimisation step of every member that is not frozen on ``B`` rows (``rows``, ``targets`` as ``Trainer.step``
+        takes them, shared by the members).  ``weights``: float32 ``[members, >= B]`` on the device, row m member m's weights
+        in batch order; None runs every member unweighted.  Enqueued on the current stream."""
+        x, ldx, r, t, w, ldw, b = self._batch(X, rows, targets, B, weights)
+        _lib.check(self._lib.bd_bank_step(self._handle, x, ldx, r, t, w, ldw, b, self._stream()))
+
+    def loss_into(self, X, rows, targets, B: int, out, weights=None) -> None:
+        """Forward pass and every member's mean (weighted, still divided by ``B``) loss of the batch into the device floats
+        ``out[:members]`` (no synchronisation)."""
+        import torch
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < self.n_members or out.device != self.device:
+            raise ValueError("out must be a contiguous float32 tensor of at least `members` entries on the bank's device")
+        x, ldx, r, t, w, ldw, b = self._batch(X, rows, targets, B, weights)
+        _lib.check(self._lib.bd_bank_loss(self._handle, x, ldx, r, t, w, ldw, b, C.c_void_p(out.data_ptr()), self._stream()))
+
+    def forward_into(self, X, rows, B: int, out) -> None:
+        """Every member's logits of the batch into the device matrix ``out`` ``[>= B, >= members * C]``: member m's in columns
+        ``m C .. m C + C`` (no synchronisation)."""
+        import torch
+        if out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < B \
+                or out.shape[1] < self.n_members * self.n_out or out.device != self.device or out.stride(0) < out.shape[1]:
+            raise ValueError("out must be a float32 [>= B, >= members * C] matrix on the bank's device with unit column stride")
+        x, ldx, r, _, _, _, b = self._batch(X, rows, None, B)
+        _lib.check(self._lib.bd_bank_forward(self._handle, x, ldx, r, b, C.c_void_p(out.data_ptr()), out.stride(0), self._stream()))
+
+    def set_learning_rate(self, member: int, learning_rate: float) -> None:
+        """Member ``member``'s learning rate of the steps from now on."""
+        _lib.check(self._lib.bd_bank_set_learning_rate(self._handle, int(member), float(learning_rate)))
+
+    def set_weight_decay(self, member: int, weight_decay: float) -> None:
+        """Member ``member``'s decoupled decay of the steps from now on (0 switches it off)."""
+        _lib.check(self._lib.bd_bank_set_weight_decay(self._handle, int(member), float(weight_decay)))
+
+    def freeze(self, member: int, frozen: bool = True) -> None:
+        """A frozen member's parameters, slots, step count, gradients and running loss stay as they are while the others
+        step; ``loss_into`` and ``forward_into`` still report it."""
+        _lib.check(self._lib.bd_bank_set_frozen(self._handle, int(member), 1 if frozen else 0))
+
+    def snapshot(self, member: int) -> None:
+        """Copy the member's parameters (not Adam's slots, not the step count) to its snapshot, on the current stream."""
+        _lib.check(self._lib.bd_bank_snapshot(self._handle, int(member), self._stream()))
+
+    def restore(self, member: int) -> None:
+        """Copy the member's last ``snapshot`` back over its parameters, on the current stream; an error if it has none."""
+        _lib.check(self._lib.bd_bank_restore(self._handle, int(member), self._stream()))
+
+    def _pair(self, fn, member: int) -> Tuple[np.ndarray, np.ndarray]:
+        w, b = np.empty((_lib.EMBEDDING_SIZE, self.n_out), dtype=np.float32), np.empty(self.n_out, dtype=np.float32)
+        _lib.check(fn(self._handle, int(member), w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        return w, b
+
+    def read(self, member: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(kernel, bias) of the member as they stand."""
+        return self._pair(self._lib.bd_bank_read, member)
+
+    def gradients(self, member: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(dW, db) of the member's last step."""
+        return self._pair(self._lib.bd_bank_gradients, member)
+
+    def mean_loss(self, reset: bool = True) -> np.ndarray:
+        """float32[members]: every member's mean training loss per row over its steps since the last reset."""
+        out = np.empty(self.n_members, dtype=np.float32)
+        _lib.check(self._lib.bd_bank_mean_loss(self._handle, 1 if reset else 0, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def workspace_fill(self, pattern: int) -> None:
+        _lib.check(self._lib.bd_bank_workspace_fill(self._handle, pattern))
+
+    def workspace(self) -> np.ndarray:
+        out = np.empty(_lib.check(self._lib.bd_bank_workspace_floats(self._handle)), dtype=np.float32)
+        _lib.check(self._lib.bd_bank_workspace_read(self._handle, out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
 
@@ -521,6 +684,396 @@ def fit_head(embeddings, targets, classes, hidden=(), activations=(), loss="cate
     finally:
         trainer.close()
     return FitResult(weights.HeadWeights(out, classes, source="fit_head"), history, best_epoch, stopped_epoch)
+
+
+MEMBER_KEYS = ("learning_rate", "weight_decay", "sample_weight", "class_weight", "early_stopping", "validation_weight")
+
+
+def check_members(members, classes, loss, epochs, targets, val_rows=None):
+    """What ``fit_heads`` refuses about its members, before any device work: ``check_fit_weighting`` of each, with the member's
+    index in front of the message.  ``targets`` as ``check_fit_arguments`` returned them, ``val_rows`` the validation set's
+    rows (None: there is none)."""
+    members = list(members)
+    if not members:
+        raise ValueError("members must hold at least one dict")
+    if len(members) > _lib.BANK_MAX_MEMBERS:
+        raise ValueError(f"{len(members)} members; a bank holds at most {_lib.BANK_MAX_MEMBERS}")
+    checked = []
+    for i, member in enumerate(members):
+        if not isinstance(member, dict):
+            raise ValueError(f"members[{i}] must be a dict, not {type(member).__name__}")
+        unknown = sorted(set(member) - set(MEMBER_KEYS), key=str)
+        if unknown:
+            raise ValueError(f"members[{i}] has unknown keys {unknown}; a member may set {', '.join(MEMBER_KEYS)}")
+        if member.get("validation_weight") is not None and val_rows is None:
+            raise ValueError(f"members[{i}] has a validation_weight, but there is no validation set")
+        try:
+            checked.append(check_fit_weighting(classes, loss, epochs, member.get("learning_rate", 1e-3), targets, val_rows or 0,
+                                               member.get("validation_weight"), member.get("sample_weight"),
+                                               member.get("class_weight"), member.get("weight_decay", 0.0),
+                                               member.get("early_stopping")))
+        except ValueError as exc:
+            raise ValueError(f"members[{i}]: {exc}") from None
+    return checked
+
+
+def _member_fit_arguments(member, validation):
+    """The keyword arguments with which ``fit_head`` runs a member of ``fit_heads`` on its own."""
+    kw = {k: v for k, v in member.items() if k != "validation_weight"}
+    if validation is not None:
+        vw = member.get("validation_weight")
+        kw["validation"] = tuple(validation[:2]) + ((vw,) if vw is not None else ())
+    return kw
+
+
+def fit_heads(embeddings, targets, classes, members, *, hidden=(), activations=(), loss="categorical", optimizer="adam", epochs=10,
+              batch_size=256, seed=0, validation=None, device=None) -> List[FitResult]:
+    """Fit ``len(members)`` heads ``1024 -> len(classes)`` in one pass over the data: the folds of a cross-validation, the
+    entries of a sweep.  ``members`` is a list of dicts; a member may set ``learning_rate`` (float, sequence or callable),
+    ``weight_decay``, ``sample_weight``, ``class_weight``, ``early_stopping`` - each as ``fit_head`` takes it - and
+    ``validation_weight``, its own weights of the shared ``validation = (embeddings, targets)`` rows.  Everything else is
+    shared: data, loss, optimizer, epochs, batch size and seed.
+
+    ``fit_heads(..., members)[m]`` has the head bytes, ``history``, ``best_epoch`` and ``stopped_epoch`` of
+    ``fit_head(embeddings, targets, classes, **shared, **members[m])`` with the member's ``validation_weight`` as the third
+    element of ``validation``.  One ``np.random.default_rng(seed)`` gives the Glorot values, then one permutation per epoch:
+    all members start equal and see the same batches, so each step gathers its rows of X once for all of them
+    (``TrainerBank``).  An epoch has one host read - M training losses and M validation sums; early stopping is decided per
+    member at that read: an improving member is snapshot, one out of patience is frozen, and the loop ends when every member
+    is frozen or the epochs are done.
+
+    ``hidden`` stacks are outside the bank: the members then run one after another through ``fit_head`` - same results, no
+    sharing.  ``ValueError`` before any device work, with the member's index: an unknown key and whatever ``fit_head`` refuses."""
+    members = list(members)
+    classes, widths, acts, (n, host, dev, t_host), val = check_fit_arguments(
+        embeddings, targets, classes, hidden, activations, loss, optimizer, 1e-3, epochs, batch_size, validation)
+    if validation is not None and len(validation) != 2:
+        raise ValueError("validation must be (embeddings, targets): a member's weights of those rows are its validation_weight")
+    checked = check_members(members, classes, loss, epochs, t_host, val[0] if val is not None else None)
+    if len(widths) > 1:
+        return [fit_head(embeddings, targets, classes, hidden=hidden, activations=activations, loss=loss, optimizer=optimizer,
+                         epochs=epochs, batch_size=batch_size, seed=seed, device=device, **_member_fit_arguments(m, validation))
+                for m in members]
+    if widths[0] > _lib.TRAIN_FUSED_MAX_WIDTH:
+        raise ValueError(f"a bank holds heads of at most {_lib.TRAIN_FUSED_MAX_WIDTH} classes, not {widths[0]}")
+    import torch
+    M = len(members)
+    rng = np.random.default_rng(seed)
+    kernel, bias, _ = glorot_layers(rng, widths, acts)[0]
+    batch = int(batch_size)
+    rates = [c[2] for c in checked]
+    stops = [c[4] for c in checked]
+    bank = TrainerBank([(kernel, bias)] * M, loss, optimizer, rates[0][0], max_batch=batch,
+                       device=device if device is not None else (dev.device.index if dev is not None else None))
+    best_epoch: List[Optional[int]] = [None] * M
+    stopped_epoch: List[Optional[int]] = [None] * M
+    try:
+        with torch.cuda.device(bank.device):
+            def resident(h, d):
+                x = d if d is not None else torch.from_numpy(h)
+                x = x.to(bank.device)
+                return x if x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 else x.contiguous().clone()
+
+            def stacked(rows_of, length):                # [M, length]: a member without weights weighs every row 1
+                if all(w is None for w in rows_of):
+                    return None
+                return torch.from_numpy(np.stack([w if w is not None else np.ones(length, dtype=np.float32) for w in rows_of])
+                                        ).to(bank.device)
+
+            for m, c in enumerate(checked):
+                if c[3]:
+                    bank.set_weight_decay(m, c[3])
+            X = resident(host, dev)
+            T = torch.from_numpy(t_host).to(bank.device)
+            Wt = stacked([c[0] for c in checked], n)
+            w_epoch = VW = None
+            if val is not None:
+                VX = X if validation[0] is embeddings else resident(val[1], val[2])
+                VT = torch.from_numpy(val[3]).to(bank.device)
+                VW = stacked([c[1] for c in checked], val[0])
+                val_words = torch.zeros(M, dtype=torch.float32, device=bank.device)
+                val_sums = torch.zeros(M, dtype=torch.float64, device=bank.device)
+            histories: List[Dict[str, List[float]]] = [{"loss": [], **({"val_loss": []} if val is not None else {})} for _ in range(M)]
+            best, waited, active = [float("inf")] * M, [0] * M, [True] * M
+            for epoch in range(int(epochs)):
+                for m in range(M):
+                    if active[m]:
+                        bank.set_learning_rate(m, rates[m][epoch])
+                perm = torch.from_numpy(rng.permutation(n).astype(np.int32)).to(bank.device)
+                t_epoch = T[perm.long()].contiguous()
+                if Wt is not None:
+                    w_epoch = Wt[:, perm.long()].contiguous()
+                for at in range(0, n, batch):
+                    b = min(batch, n - at)
+                    bank.step(X, perm[at:at + b], t_epoch[at:at + b], b, w_epoch[:, at:at + b] if Wt is not None else None)
+                if val is not None:
+                    val_sums.zero_()
+                    for at in range(0, val[0], batch):
+                        b = min(batch, val[0] - at)
+                        bank.loss_into(VX[at:at + b], None, VT[at:at + b], b, val_words, VW[:, at:at + b] if VW is not None else None)
+                        val_sums.add_(val_words.double(), alpha=b)
+                losses = bank.mean_loss(reset=True)               # the one read of the epoch (waits for the stream)
+                val_losses = val_sums.cpu().numpy() if val is not None else None
+                for m in range(M):
+                    if not active[m]:
+                        continue
+                    histories[m]["loss"].append(float(losses[m]))
+                    if val is not None:
+                        histories[m]["val_loss"].append(float(val_losses[m]) / val[0])
+                    if stops[m] is not None:
+                        patience, min_delta, _ = stops[m]
+                        monitored = histories[m]["val_loss" if val is not None else "loss"][-1]
+                        stopped_epoch[m] = epoch
+                        if monitored < best[m] - min_delta:
+                            best[m], best_epoch[m], waited[m] = monitored, epoch, 0
+                            bank.snapshot(m)
+                        else:
+                            waited[m] += 1
+                            if waited[m] >= patience:
+                                active[m] = False
+                                bank.freeze(m)
+                if not any(active):
+                    break
+            out = []
+            for m in range(M):
+                if stops[m] is not None and stops[m][2] and best_epoch[m] is not None and best_epoch[m] != stopped_epoch[m]:
+                    bank.restore(m)
+                out.append(FitResult(weights.HeadWeights([bank.read(m) + (acts[0],)], classes, source="fit_head"), histories[m],
+                                     best_epoch[m], stopped_epoch[m]))
+    finally:
+        bank.close()
+    return out
+
+
+FOLD_SEED_STREAM = 0x666F6C64               # the fold builder's generator is default_rng([seed, this]): not the fit's default_rng(seed)
+
+
+def build_folds(targets, loss: str = "categorical", folds: int = 5, groups=None, seed: int = 0) -> np.ndarray:
+    """int32[N]: the fold that holds each row out, built from ``np.random.default_rng([seed, FOLD_SEED_STREAM])`` - a generator
+    of its own, so the fit's draws from ``default_rng(seed)`` do not move.
+
+    * without ``groups``, categorical loss: stratified - the rows of each class are shuffled and dealt round-robin, the deal of
+      a class starting where the last one ended, so per class the folds' counts differ by at most 1;
+    * without ``groups``, binary loss: all rows shuffled and dealt round-robin;
+    * with ``groups`` (``[N]``, any hashable: the recording a window came from): whole groups are dealt, largest first (ties in
+      shuffled order), each to the fold that holds the fewest rows so far (ties: the lowest fold).  No group is split; labels
+      are not looked at.
+
+    ``ValueError``: fewer than 2 folds, more folds than groups or rows, a fold left without rows."""
+    t = np.asarray(targets)
+    n = t.shape[0]
+    if isinstance(folds, bool) or not isinstance(folds, (int, np.integer)) or folds < 2:
+        raise ValueError("folds must be an integer >= 2")
+    folds = int(folds)
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+        raise ValueError("seed must be a non-negative integer")
+    rng = np.random.default_rng([int(seed), FOLD_SEED_STREAM])
+    fold_of_row = np.full(n, -1, dtype=np.int32)
+    if groups is not None:
+        groups = list(groups) if not isinstance(groups, np.ndarray) else groups.tolist()
+        if len(groups) != n:
+            raise ValueError(f"groups must name one group per row ({n}), not {len(groups)}")
+        index: Dict[Any, int] = {}
+        group_of_row = np.array([index.setdefault(g, len(index)) for g in groups], dtype=np.int64)
+        if folds > len(index):
+            raise ValueError(f"{folds} folds but only {len(index)} groups: a group is never split")
+        size = np.bincount(group_of_row, minlength=len(index))
+        order = rng.permutation(len(index))
+        order = order[np.argsort(-size[order], kind="stable")]
+        held = np.zeros(folds, dtype=np.int64)
+        fold_of_group = np.empty(len(index), dtype=np.int32)
+        for g in order:
+            k = int(np.argmin(held))
+            fold_of_group[g] = k
+            held[k] += size[g]
+        fold_of_row = fold_of_group[group_of_row]
+    else:
+        if folds > n:
+            raise ValueError(f"{folds} folds but only {n} rows")
+        strata = [np.flatnonzero(t == c) for c in np.unique(t)] if loss == "categorical" else [np.arange(n)]
+        start = 0
+        for rows in strata:
+            rows = rows[rng.permutation(rows.size)]
+            fold_of_row[rows] = (start + np.arange(rows.size)) % folds
+            start = (start + rows.size) % folds
+    empty = [k for k in range(folds) if not (fold_of_row == k).any()]
+    if empty:
+        raise ValueError(f"fold {empty[0]} holds no rows")
+    return fold_of_row.astype(np.int32)
+
+
+def check_folds(fold_of_row, n: int) -> Tuple[np.ndarray, int]:
+    """A caller's ``fold_of_row`` as (int32[N], K): integers 0..K-1, K = the largest + 1 >= 2, every fold with rows."""
+    f = np.asarray(fold_of_row.detach().cpu().numpy() if _is_torch(fold_of_row) else fold_of_row)
+    if f.shape != (n,) or f.dtype.kind not in "iu":
+        raise ValueError(f"fold_of_row must be integers of shape ({n},), not {f.dtype} {f.shape}")
+    if f.min() < 0 or f.max() >= _lib.BANK_MAX_MEMBERS:
+        raise ValueError(f"fold_of_row must lie in 0..K-1 (K <= {_lib.BANK_MAX_MEMBERS}); found {int(f.min())}..{int(f.max())}")
+    k = int(f.max()) + 1
+    if k < 2:
+        raise ValueError("fold_of_row names one fold only: nothing would be left to train on")
+    empty = [i for i in range(k) if not (f == i).any()]
+    if empty:
+        raise ValueError(f"fold {empty[0]} holds no rows")
+    return f.astype(np.int32), k
+
+
+def fold_members(targets, classes, loss, fold_of_row, folds: int, entry: Dict[str, Any]) -> List[Dict[str, Any]]:
+    """The ``fit_heads`` members of one grid entry, fold 0 .. folds-1.  Member k trains with ``sample_weight_r x [fold_of_row[r]
+    != k]`` and validates on the same rows with weight ``[fold_of_row[r] == k]``; its class weights - "balanced" included -
+    are computed from the labels of its training side only and handed on as an explicit float64 vector."""
+    n = len(fold_of_row)
+    base = entry.get("sample_weight")
+    if base is not None:
+        base = _check_weights(base, n, "sample_weight").astype(np.float64)
+    out = []
+    for k in range(folds):
+        train_side = fold_of_row != k
+        member = {key: entry[key] for key in ("learning_rate", "weight_decay", "early_stopping") if key in entry}
+        member["sample_weight"] = train_side.astype(np.float64) if base is None else base * train_side
+        cw = entry.get("class_weight")
+        if cw is not None:
+            if loss != "categorical":
+                raise ValueError('class_weight needs loss="categorical": multi-hot targets have no one class per row; '
+                                 "weigh the rows with sample_weight instead")
+            if isinstance(cw, str):
+                if cw != "balanced":
+                    raise ValueError(f'class_weight must be "balanced", a dict or a sequence, not "{cw}"')
+                cw = balanced_class_weights(np.asarray(targets)[train_side], len(classes))
+            elif isinstance(cw, dict):
+                unknown = [name for name in cw if name not in classes]
+                if unknown:
+                    raise ValueError(f"class_weight names unknown classes {unknown}; the classes are {list(classes)}")
+                cw = np.array([cw.get(name, 1.0) for name in classes], dtype=np.float64)
+            member["class_weight"] = cw
+        member["validation_weight"] = (~train_side).astype(np.float32)
+        out.append(member)
+    return out
+
+
+@dataclass
+class CrossValidationEntry:
+    """One grid entry of ``cross_validate_head``.  ``oof_logits`` [N, C]: row r from the member that held r out.  ``fits``: the K
+    folds' ``FitResult``.  ``fold_best``: per fold the monitored ``val_loss`` of its best epoch (with ``early_stopping``) or
+    its lowest (without)."""
+    oof_logits: np.ndarray
+    fits: List[FitResult]
+    fold_best: List[float]
+    classes: List[str]
+    positives: np.ndarray = field(repr=False, default=None)      # bool [N, C]
+
+    def metrics(self, class_name: str) -> str:
+        """``metrics_table`` of the out-of-fold logits of ``class_name`` against its rows: the text of ``tests/metrics.csv``."""
+        if class_name not in self.classes:
+            raise ValueError(f'no class "{class_name}"; the classes are {self.classes}')
+        c = self.classes.index(class_name)
+        return metrics_table(self.oof_logits[:, c], self.positives[:, c])
+
+
+@dataclass
+class CrossValidation:
+    """``entries[g]`` belongs to ``grid[g]``; ``best`` is the grid index with the lowest mean of the folds' best ``val_loss``."""
+    fold_of_row: np.ndarray
+    grid: List[Dict[str, Any]]
+    entries: List[CrossValidationEntry]
+    best: int
+
+
+def _fold_best(fit: FitResult) -> float:
+    v = np.asarray(fit.history["val_loss"], dtype=np.float64)
+    if fit.best_epoch is not None:
+        return float(v[fit.best_epoch])
+    return float(np.nanmin(v)) if np.isfinite(v).any() else float("inf")
+
+
+def check_cross_validation(targets, classes, loss, folds, groups, fold_of_row, grid, seed, shared_member):
+    """What ``cross_validate_head`` refuses about folds and grid, before any device work; ``targets`` as ``check_fit_arguments``
+    returned them.  Returns (fold_of_row int32[N], K, grid as a list, the members, grid-major: entry g's fold k at g K + k)."""
+    n = len(targets)
+    if fold_of_row is not None:
+        if folds is not None or groups is not None:
+            raise ValueError("fold_of_row already says which fold holds each row out: give it, or folds / groups, not both")
+        fold_of_row, k = check_folds(fold_of_row, n)
+    else:
+        k = 5 if folds is None else folds
+        fold_of_row = build_folds(targets, loss, k, groups, seed)
+        k = int(k)
+    if loss == "categorical":
+        for fold in range(k):
+            count = np.bincount(np.asarray(targets)[fold_of_row != fold], minlength=len(classes))
+            if (count == 0).any():
+                c = int(np.flatnonzero(count == 0)[0])
+                raise ValueError(f'the training side of fold {fold} has no row of class {c} ("{classes[c]}")')
+    grid = list(grid)
+    if not grid:
+        raise ValueError("grid must hold at least one dict ({} fits with the defaults)")
+    members = []
+    for g, entry in enumerate(grid):
+        if not isinstance(entry, dict):
+            raise ValueError(f"grid[{g}] must be a dict, not {type(entry).__name__}")
+        unknown = sorted(set(entry) - set(MEMBER_KEYS[:-1]), key=str)
+        if unknown:
+            raise ValueError(f"grid[{g}] has unknown keys {unknown}; an entry may set {', '.join(MEMBER_KEYS[:-1])}")
+        try:
+            members += fold_members(targets, classes, loss, fold_of_row, k, {**shared_member, **entry})
+        except ValueError as exc:
+            raise ValueError(f"grid[{g}]: {exc}") from None
+    if len(members) > _lib.BANK_MAX_MEMBERS:
+        raise ValueError(f"{k} folds x {len(grid)} grid entries = {len(members)} members; a bank holds at most {_lib.BANK_MAX_MEMBERS}")
+    return fold_of_row, k, grid, members
+
+
+def cross_validate_head(embeddings, targets, classes, *, folds=None, groups=None, fold_of_row=None, grid=({},), loss="categorical",
+                        optimizer="adam", epochs=10, batch_size=256, seed=0, device=None, **shared) -> CrossValidation:
+    """Grouped, stratified k-fold cross-validation of ``fit_head`` over a grid of its knobs, every fold of every grid entry
+    fitted in one pass (``fit_heads``): out-of-fold logits for an honest ``metrics_table``, and the grid entry to refit with.
+
+    Folds: ``fold_of_row`` (``int[N]`` in 0..K-1, the caller's), or ``folds`` (5 when not given) built by ``build_folds`` from
+    ``seed`` and, if given, ``groups``.  Giving ``fold_of_row`` and ``folds`` / ``groups`` is an error, and so is a fold without
+    rows and - categorical loss - a training side that lacks a class.
+
+    ``grid``: dicts of ``learning_rate``, ``weight_decay``, ``sample_weight``, ``class_weight``, ``early_stopping``; ``shared``
+    may set the same keys for every entry.  Member (k, g) is ``fold_members(...)[k]`` of entry g - a call ``fit_head`` can
+    express, and bit for bit that call.  Two consequences of a fold being row weights: held-out rows still count in Keras's
+    ``sum_over_batch_size`` denominator, so a fold's gradient is about (K-1)/K of a fit's on the training rows alone; and
+    ``val_loss`` is n_heldout / N times the held-out rows' mean loss.
+
+    The result's ``entries[g]`` hold ``oof_logits``, the K ``FitResult``, ``fold_best`` and ``metrics(class_name)``; ``best`` is
+    the entry with the lowest mean ``fold_best``.  The final model stays the caller's own ``fit_head`` on all rows with
+    ``grid[best]``.  Hidden layers are outside the bank and not offered here."""
+    unknown = sorted(set(shared) - set(MEMBER_KEYS[:-1]))
+    if unknown:
+        raise ValueError(f"unknown arguments {unknown}")
+    classes, widths, acts, (n, host, dev, t_host), _ = check_fit_arguments(
+        embeddings, targets, classes, (), (), loss, optimizer, 1e-3, epochs, batch_size, None)
+    fold_of_row, k, grid, members = check_cross_validation(t_host, classes, loss, folds, groups, fold_of_row, grid, seed, shared)
+    fits = fit_heads(embeddings, targets, classes, members, loss=loss, optimizer=optimizer, epochs=epochs, batch_size=batch_size,
+                     seed=seed, validation=(embeddings, targets), device=device)
+    import torch
+    batch = int(batch_size)
+    bank = TrainerBank([f.head.layers[0][:2] for f in fits], loss, optimizer, max_batch=batch,
+                       device=device if device is not None else (dev.device.index if dev is not None else None))
+    try:
+        with torch.cuda.device(bank.device):
+            X = (dev if dev is not None else torch.from_numpy(host)).to(bank.device)
+            if not (X.stride(1) == 1 and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0):
+                X = X.contiguous().clone()
+            c = len(classes)
+            logits = torch.empty((n, len(members) * c), dtype=torch.float32, device=bank.device)
+            for at in range(0, n, batch):
+                b = min(batch, n - at)
+                bank.forward_into(X[at:at + b], None, b, logits[at:at + b])
+            logits = logits.cpu().numpy().reshape(n, len(members), c)
+    finally:
+        bank.close()
+    positives = (t_host[:, None] == np.arange(c)[None, :]) if loss == "categorical" else (t_host != 0)
+    entries = []
+    for g in range(len(grid)):
+        entry_fits = fits[g * k:(g + 1) * k]
+        oof = logits[np.arange(n), g * k + fold_of_row, :].copy()
+        entries.append(CrossValidationEntry(oof, entry_fits, [_fold_best(f) for f in entry_fits], classes, positives))
+    best = int(np.argmin([np.mean(e.fold_best) for e in entries]))
+    return CrossValidation(fold_of_row, grid, entries, best)
 
 
 def _num(x: float) -> str:
