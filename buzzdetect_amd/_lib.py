@@ -260,6 +260,28 @@ BANK_PROTOTYPES = {
     "bd_bank_workspace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
 }
 
+MIX_ABI_VERSION = 1
+MIX_SLICE = 4096
+MIX_POWER_FLOOR = 1e-20
+MIX_FLAG_SILENT_BACKGROUND = 1
+MIX_MAX_CLIPS = 65536
+
+
+class bd_mix_clip(C.Structure):
+    _fields_ = [("ev_off", C.c_int64), ("nz_off", C.c_int64), ("out_off", C.c_int64), ("n", C.c_int32), ("ev_gain", C.c_float),
+                ("ratio", C.c_float)]
+
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_mix.h
+MIX_PROTOTYPES = {
+    "bd_mix_abi_version": (C.c_int, []),
+    "bd_mix_workspace_bytes": (C.c_int64, [C.POINTER(bd_mix_clip), C.c_int32]),
+    "bd_mix": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(bd_mix_clip), C.c_int32, C.c_void_p, C.c_int64,
+                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_mix_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(bd_mix_clip), C.c_int32, C.c_void_p,
+                              C.c_int64, C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -293,7 +315,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     lib = C.CDLL(path)
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
             + list(HEAD_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
-            + list(BANK_PROTOTYPES.items()):
+            + list(BANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -311,6 +333,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: trainer ABI version {lib.bd_train_abi_version()} != {TRAIN_ABI_VERSION}; rebuild")
     if lib.bd_bank_abi_version() != BANK_ABI_VERSION:
         raise RuntimeError(f"{path}: head-bank ABI version {lib.bd_bank_abi_version()} != {BANK_ABI_VERSION}; rebuild")
+    if lib.bd_mix_abi_version() != MIX_ABI_VERSION:
+        raise RuntimeError(f"{path}: mixer ABI version {lib.bd_mix_abi_version()} != {MIX_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

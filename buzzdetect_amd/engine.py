@@ -506,14 +506,41 @@ class HipEngine:
         from .pcmio import PcmTrack
         return self._read_decoded(PcmTrack(path), start, frames)
 
-    def _read_decoded(self, track, start: int, frames: Optional[int]) -> torch.Tensor:
-        """read_flac / read_pcm: the range staged and decoded piece by piece by the track's device decoder; closes the track."""
+    def read_audio(self, source, start: int = 0, frames: Optional[int] = None, raw: bool = False) -> torch.Tensor:
+        """Frames [start, start + frames) of any recording ``analyze`` reads (``flacio.open_track``: WAV, FLAC, pcmio's formats;
+        default: to its end) as a device tensor [frames, channels]: float32 as soundfile.read(dtype="float32") gives them, or
+        with ``raw`` the layout of the feeder's chunk slots - 16-bit sources as int16, which ``resample`` takes as they are.
+        ``source``: a path, or an open track, which stays open.  Fewer frames come back where the file ends early."""
+        from .flacio import open_track
+        own = isinstance(source, (str, os.PathLike))
+        track = open_track(os.fspath(source)) if own else source
+        if hasattr(track, "pieces"):                       # FlacTrack / PcmTrack: decoded on the device
+            return self._read_decoded(track, start, frames, raw=raw, close=own)
+        try:                                               # WavTrack: as the feeder's _fill_wav reads it
+            start = min(max(int(start), 0), track.frames)
+            n = track.frames - start if frames is None else max(0, min(int(frames), track.frames - start))
+            bpf = track.bytes_per_frame
+            host = np.empty(max(n * bpf, 1), np.uint8)
+            got = track.read_raw_into(start, n, host)
+            if track.is_s16:
+                a = host[: got * bpf].view("<i2").reshape(-1, track.channels)
+            else:
+                a = track.convert(host[: got * bpf])
+            t = torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            return t.to(torch.float32) / 32768.0 if track.is_s16 and not raw else t
+        finally:
+            if own:
+                track.close()
+
+    def _read_decoded(self, track, start: int, frames: Optional[int], raw: bool = False, close: bool = True) -> torch.Tensor:
+        """read_flac / read_pcm: the range staged and decoded piece by piece by the track's device decoder; closes the track
+        unless told not to.  ``raw``: 16-bit audio stays int16."""
         try:
             start = min(max(int(start), 0), track.frames)
             n = track.frames - start if frames is None else min(int(frames), track.frames - start)
             out = torch.empty((max(n, 0), track.channels), dtype=torch.int16 if track.is_s16 else torch.float32, device=self.device)
             if n <= 0:
-                return out.to(torch.float32)
+                return out if raw else out.to(torch.float32)
             stream = self._stream()
             dec = track.decoder(torch, self.device)
             bpf = out.element_size() * track.channels
@@ -531,9 +558,10 @@ class HipEngine:
                 if k < m:
                     break
         finally:
-            track.close()
+            if close:
+                track.close()
         out = out[:got]
-        return out.to(torch.float32) / 32768.0 if track.is_s16 else out
+        return out.to(torch.float32) / 32768.0 if track.is_s16 and not raw else out
 
     # ------------------------------------------------------------------ hot path
     def frontend(self, samples, hop: int) -> torch.Tensor:
