@@ -260,6 +260,33 @@ BANK_PROTOTYPES = {
     "bd_bank_workspace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
 }
 
+STACKBANK_ABI_VERSION = 1
+STACKBANK_MAX_WORKSPACE_BYTES = 1 << 33
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_stackbank.h
+STACKBANK_PROTOTYPES = {
+    "bd_stackbank_abi_version": (C.c_int, []),
+    "bd_stackbank_create": (C.c_int, [C.c_int, C.POINTER(bd_head_layer), C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(bd_train_optimizer), C.c_int32, C.POINTER(C.c_void_p)]),
+    "bd_stackbank_destroy": (C.c_int, [C.c_void_p]),
+    "bd_stackbank_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                    C.c_void_p]),
+    "bd_stackbank_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                    C.c_void_p, C.c_void_p]),
+    "bd_stackbank_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_stackbank_set_learning_rate": (C.c_int, [C.c_void_p, C.c_int32, C.c_float]),
+    "bd_stackbank_set_weight_decay": (C.c_int, [C.c_void_p, C.c_int32, C.c_float]),
+    "bd_stackbank_set_frozen": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "bd_stackbank_snapshot": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_stackbank_restore": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_stackbank_read": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_stackbank_gradients": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_stackbank_mean_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_stackbank_workspace_floats": (C.c_int64, [C.c_void_p]),
+    "bd_stackbank_workspace_fill": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "bd_stackbank_workspace_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+}
+
 MIX_ABI_VERSION = 1
 MIX_SLICE = 4096
 MIX_POWER_FLOOR = 1e-20
@@ -315,7 +342,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     lib = C.CDLL(path)
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
             + list(HEAD_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
-            + list(BANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()):
+            + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -333,6 +360,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: trainer ABI version {lib.bd_train_abi_version()} != {TRAIN_ABI_VERSION}; rebuild")
     if lib.bd_bank_abi_version() != BANK_ABI_VERSION:
         raise RuntimeError(f"{path}: head-bank ABI version {lib.bd_bank_abi_version()} != {BANK_ABI_VERSION}; rebuild")
+    if lib.bd_stackbank_abi_version() != STACKBANK_ABI_VERSION:
+        raise RuntimeError(f"{path}: stack-bank ABI version {lib.bd_stackbank_abi_version()} != {STACKBANK_ABI_VERSION}; rebuild")
     if lib.bd_mix_abi_version() != MIX_ABI_VERSION:
         raise RuntimeError(f"{path}: mixer ABI version {lib.bd_mix_abi_version()} != {MIX_ABI_VERSION}; rebuild")
     _lib = lib

@@ -1,5 +1,6 @@
 """Fit a classifier head on the GPU and save it as a model directory (include/buzzdetect_train.h, csrc/headtrain.hip;
-many heads at once: include/buzzdetect_bank.h, csrc/headbank.hip).
+many heads at once: include/buzzdetect_bank.h, csrc/headbank.hip; many stacks at once: include/buzzdetect_stackbank.h,
+csrc/stackbank.hip).
 
 The bring-your-own-labels loop without a foreign toolchain:
 
@@ -34,6 +35,11 @@ stands for, each step's rows gathered once for all of them - and ``cross_validat
 groups=recordings, grid=[...])`` builds grouped, stratified folds, fits every (fold, grid entry) that way and returns
 out-of-fold logits, ``metrics(class_name)`` for an honest threshold, and the grid entry to refit on all rows.  A fold is row
 weights: held-out rows weigh 0 while fitting and are the only ones that weigh in ``val_loss``.
+
+Heads with hidden layers, or with more than 64 classes, go the same way through a bank of whole stacks
+(include/buzzdetect_stackbank.h, csrc/stackbank.hip): ``fit_stacks(..., hidden=(128,), activations=("relu",))`` and
+``cross_validate_stack(...)`` are ``fit_heads`` and ``cross_validate_head`` with a shape, every member bit for bit its
+``fit_head`` call.
 
 Out of scope: dropout, penalties added to the loss, a per-class ``pos_weight`` for the binary loss, focal loss and label
 smoothing, resuming a fit from a snapshot, ``.keras`` / ``.h5`` output, multi-GPU training, and training anything below the
@@ -230,6 +236,11 @@ class TrainerBank:
     slots, rate, decay, row weights, running loss, snapshot and frozen flag.  Member m is, bit for bit, the ``Trainer`` that
     got the same calls with row m of the weights."""
 
+    _prefix = "bd_bank_"                # the C entry points the methods call: TrainerStackBank has the same ones under its own
+
+    def _call(self, name, *args):
+        return _lib.check(getattr(self._lib, self._prefix + name)(self._handle, *args))
+
     def __init__(self, members, loss: str = "categorical", optimizer: str = "adam", learning_rate: float = 1e-3,
                  beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, max_batch: int = 256,
                  device: Optional[int] = None):
@@ -270,7 +281,7 @@ class TrainerBank:
 
     def close(self) -> None:
         if getattr(self, "_handle", None) is not None and self._handle.value:
-            self._lib.bd_bank_destroy(self._handle)
+            getattr(self._lib, self._prefix + "destroy")(self._handle)
             self._handle = C.c_void_p()
 
     def __del__(self):
@@ -309,7 +320,7 @@ class TrainerBank:
         takes them, shared by the members).  ``weights``: float32 ``[members, >= B]`` on the device, row m member m's weights
         in batch order; None runs every member unweighted.  Enqueued on the current stream."""
         x, ldx, r, t, w, ldw, b = self._batch(X, rows, targets, B, weights)
-        _lib.check(self._lib.bd_bank_step(self._handle, x, ldx, r, t, w, ldw, b, self._stream()))
+        self._call("step", x, ldx, r, t, w, ldw, b, self._stream())
 
     def loss_into(self, X, rows, targets, B: int, out, weights=None) -> None:
         """Forward pass and every member's mean (weighted, still divided by ``B``) loss of the batch into the device floats
@@ -318,7 +329,7 @@ class TrainerBank:
         if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < self.n_members or out.device != self.device:
             raise ValueError("out must be a contiguous float32 tensor of at least `members` entries on the bank's device")
         x, ldx, r, t, w, ldw, b = self._batch(X, rows, targets, B, weights)
-        _lib.check(self._lib.bd_bank_loss(self._handle, x, ldx, r, t, w, ldw, b, C.c_void_p(out.data_ptr()), self._stream()))
+        self._call("loss", x, ldx, r, t, w, ldw, b, C.c_void_p(out.data_ptr()), self._stream())
 
     def forward_into(self, X, rows, B: int, out) -> None:
         """Every member's logits of the batch into the device matrix ``out`` ``[>= B, >= members * C]``: member m's in columns
@@ -328,55 +339,124 @@ class TrainerBank:
                 or out.shape[1] < self.n_members * self.n_out or out.device != self.device or out.stride(0) < out.shape[1]:
             raise ValueError("out must be a float32 [>= B, >= members * C] matrix on the bank's device with unit column stride")
         x, ldx, r, _, _, _, b = self._batch(X, rows, None, B)
-        _lib.check(self._lib.bd_bank_forward(self._handle, x, ldx, r, b, C.c_void_p(out.data_ptr()), out.stride(0), self._stream()))
+        self._call("forward", x, ldx, r, b, C.c_void_p(out.data_ptr()), out.stride(0), self._stream())
 
     def set_learning_rate(self, member: int, learning_rate: float) -> None:
         """Member ``member``'s learning rate of the steps from now on."""
-        _lib.check(self._lib.bd_bank_set_learning_rate(self._handle, int(member), float(learning_rate)))
+        self._call("set_learning_rate", int(member), float(learning_rate))
 
     def set_weight_decay(self, member: int, weight_decay: float) -> None:
         """Member ``member``'s decoupled decay of the steps from now on (0 switches it off)."""
-        _lib.check(self._lib.bd_bank_set_weight_decay(self._handle, int(member), float(weight_decay)))
+        self._call("set_weight_decay", int(member), float(weight_decay))
 
     def freeze(self, member: int, frozen: bool = True) -> None:
         """A frozen member's parameters, slots, step count, gradients and running loss stay as they are while the others
         step; ``loss_into`` and ``forward_into`` still report it."""
-        _lib.check(self._lib.bd_bank_set_frozen(self._handle, int(member), 1 if frozen else 0))
+        self._call("set_frozen", int(member), 1 if frozen else 0)
 
     def snapshot(self, member: int) -> None:
         """Copy the member's parameters (not Adam's slots, not the step count) to its snapshot, on the current stream."""
-        _lib.check(self._lib.bd_bank_snapshot(self._handle, int(member), self._stream()))
+        self._call("snapshot", int(member), self._stream())
 
     def restore(self, member: int) -> None:
         """Copy the member's last ``snapshot`` back over its parameters, on the current stream; an error if it has none."""
-        _lib.check(self._lib.bd_bank_restore(self._handle, int(member), self._stream()))
+        self._call("restore", int(member), self._stream())
 
-    def _pair(self, fn, member: int) -> Tuple[np.ndarray, np.ndarray]:
+    def _pair(self, name, member: int) -> Tuple[np.ndarray, np.ndarray]:
         w, b = np.empty((_lib.EMBEDDING_SIZE, self.n_out), dtype=np.float32), np.empty(self.n_out, dtype=np.float32)
-        _lib.check(fn(self._handle, int(member), w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        self._call(name, int(member), w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p))
         return w, b
 
     def read(self, member: int) -> Tuple[np.ndarray, np.ndarray]:
         """(kernel, bias) of the member as they stand."""
-        return self._pair(self._lib.bd_bank_read, member)
+        return self._pair("read", member)
 
     def gradients(self, member: int) -> Tuple[np.ndarray, np.ndarray]:
         """(dW, db) of the member's last step."""
-        return self._pair(self._lib.bd_bank_gradients, member)
+        return self._pair("gradients", member)
 
     def mean_loss(self, reset: bool = True) -> np.ndarray:
         """float32[members]: every member's mean training loss per row over its steps since the last reset."""
         out = np.empty(self.n_members, dtype=np.float32)
-        _lib.check(self._lib.bd_bank_mean_loss(self._handle, 1 if reset else 0, out.ctypes.data_as(C.c_void_p)))
+        self._call("mean_loss", 1 if reset else 0, out.ctypes.data_as(C.c_void_p))
         return out
 
     def workspace_fill(self, pattern: int) -> None:
-        _lib.check(self._lib.bd_bank_workspace_fill(self._handle, pattern))
+        self._call("workspace_fill", pattern)
 
     def workspace(self) -> np.ndarray:
-        out = np.empty(_lib.check(self._lib.bd_bank_workspace_floats(self._handle)), dtype=np.float32)
-        _lib.check(self._lib.bd_bank_workspace_read(self._handle, out.ctypes.data_as(C.c_void_p), out.size))
+        out = np.empty(self._call("workspace_floats"), dtype=np.float32)
+        self._call("workspace_read", out.ctypes.data_as(C.c_void_p), out.size)
         return out
+
+
+class TrainerStackBank(TrainerBank):
+    """``bd_stackbank_*`` on torch tensors (include/buzzdetect_stackbank.h): ``members`` = [[(kernel, bias, activation), ...],
+    ...] are the initial layers of M Dense stacks of one shape - what ``Trainer`` takes, M times.  ``TrainerBank``'s methods
+    with the same meaning; ``read`` and ``gradients`` take the layer as well.  Member m is, bit for bit, the ``Trainer`` that
+    got the same calls with row m of the weights."""
+
+    _prefix = "bd_stackbank_"
+
+    def __init__(self, members, loss: str = "categorical", optimizer: str = "adam", learning_rate: float = 1e-3,
+                 beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, max_batch: int = 256,
+                 device: Optional[int] = None):
+        import torch
+        self._handle = C.c_void_p()
+        self._lib = _lib.load()
+        if loss not in _lib.TRAIN_LOSSES:
+            raise ValueError(f'loss must be one of {sorted(_lib.TRAIN_LOSSES)}, not "{loss}"')
+        if optimizer not in _lib.TRAIN_OPTIMIZERS:
+            raise ValueError(f'optimizer must be one of {sorted(_lib.TRAIN_OPTIMIZERS)}, not "{optimizer}"')
+        members = [list(member) for member in members]
+        if not members or not members[0]:
+            raise ValueError("a bank needs at least one member of at least one layer")
+        n_layers = len(members[0])
+        if not torch.cuda.is_available():
+            raise RuntimeError("buzzdetect_amd: no HIP device visible to PyTorch; the trainer has no CPU path")
+        self.device_index = torch.cuda.current_device() if device is None else int(device)
+        self.device = torch.device("cuda", self.device_index)
+        self.loss = loss
+        self.max_batch = int(max_batch)
+        self.n_members = len(members)
+        arr = (_lib.bd_head_layer * (len(members) * n_layers))()
+        keep = []
+        for i, member in enumerate(members):
+            if len(member) != n_layers:
+                raise ValueError(f"member {i} has {len(member)} layers, member 0 has {n_layers}")
+            for l, (kernel, bias, activation) in enumerate(member):
+                k = np.ascontiguousarray(kernel, dtype=np.float32)
+                b = np.ascontiguousarray(bias, dtype=np.float32)
+                if k.ndim != 2 or b.shape != (k.shape[1],):
+                    raise ValueError(f"member {i}, layer {l}: a kernel [in, out] and a bias [out], not {k.shape} and {b.shape}")
+                keep += [k, b]
+                at = arr[i * n_layers + l]
+                at.kernel = k.ctypes.data_as(C.POINTER(C.c_float))
+                at.bias = b.ctypes.data_as(C.POINTER(C.c_float))
+                at.n_in, at.n_out = k.shape
+                at.activation = _lib.HEAD_ACTIVATIONS[activation]
+        self.shapes = [(int(arr[l].n_in), int(arr[l].n_out)) for l in range(n_layers)]
+        self.n_out = self.shapes[-1][1]
+        opt = _lib.bd_train_optimizer(_lib.TRAIN_OPTIMIZERS[optimizer], learning_rate, beta_1, beta_2, epsilon, 0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.bd_stackbank_create(self.device_index, arr, len(members), n_layers, _lib.TRAIN_LOSSES[loss],
+                                                     C.byref(opt), self.max_batch, C.byref(self._handle)))
+
+    def _pair(self, name, member: int, layer: int) -> Tuple[np.ndarray, np.ndarray]:
+        if not 0 <= int(layer) < len(self.shapes):
+            raise ValueError(f"no layer {layer}: the members have {len(self.shapes)}")
+        k, n = self.shapes[layer]
+        w, b = np.empty((k, n), dtype=np.float32), np.empty(n, dtype=np.float32)
+        self._call(name, int(member), int(layer), w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p))
+        return w, b
+
+    def read(self, member: int, layer: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(kernel, bias) of the member's layer as they stand."""
+        return self._pair("read", member, layer)
+
+    def gradients(self, member: int, layer: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(dW, db) of the member's layer from its last step."""
+        return self._pair("gradients", member, layer)
 
 
 def _is_torch(x) -> bool:
@@ -742,8 +822,8 @@ def fit_heads(embeddings, targets, classes, members, *, hidden=(), activations=(
     member at that read: an improving member is snapshot, one out of patience is frozen, and the loop ends when every member
     is frozen or the epochs are done.
 
-    ``hidden`` stacks are outside the bank: the members then run one after another through ``fit_head`` - same results, no
-    sharing.  ``ValueError`` before any device work, with the member's index: an unknown key and whatever ``fit_head`` refuses."""
+    ``hidden`` stacks are outside this bank: the members then run one after another through ``fit_head`` - same results, no
+    sharing; ``fit_stacks`` fits them in one pass, and one-layer heads of more than 64 classes too.  ``ValueError`` before any device work, with the member's index: an unknown key and whatever ``fit_head`` refuses."""
     members = list(members)
     classes, widths, acts, (n, host, dev, t_host), val = check_fit_arguments(
         embeddings, targets, classes, hidden, activations, loss, optimizer, 1e-3, epochs, batch_size, validation)
@@ -756,15 +836,51 @@ def fit_heads(embeddings, targets, classes, members, *, hidden=(), activations=(
                 for m in members]
     if widths[0] > _lib.TRAIN_FUSED_MAX_WIDTH:
         raise ValueError(f"a bank holds heads of at most {_lib.TRAIN_FUSED_MAX_WIDTH} classes, not {widths[0]}")
-    import torch
-    M = len(members)
     rng = np.random.default_rng(seed)
     kernel, bias, _ = glorot_layers(rng, widths, acts)[0]
-    batch = int(batch_size)
+    bank = TrainerBank([(kernel, bias)] * len(members), loss, optimizer, checked[0][2][0], max_batch=int(batch_size),
+                       device=device if device is not None else (dev.device.index if dev is not None else None))
+    return _fit_members(bank, checked, rng, (n, host, dev, t_host), val, validation is not None and validation[0] is embeddings,
+                        int(epochs), int(batch_size), classes, lambda m: [bank.read(m) + (acts[0],)])
+
+
+def fit_stacks(embeddings, targets, classes, members, *, hidden=(), activations=(), loss="categorical", optimizer="adam", epochs=10,
+               batch_size=256, seed=0, validation=None, device=None) -> List[FitResult]:
+    """``fit_heads`` for heads of any shape ``fit_head`` takes: ``len(members)`` stacks ``1024 -> hidden... -> len(classes)``
+    fitted in one pass (``TrainerStackBank``: include/buzzdetect_stackbank.h).  ``members`` and everything shared are as
+    ``fit_heads`` takes them, and so are the checks, with ``members[i]:`` in front of a member's error.
+
+    ``fit_stacks(..., members)[m]`` has the head bytes of every layer, ``history``, ``best_epoch`` and ``stopped_epoch`` of
+    ``fit_head(embeddings, targets, classes, hidden=hidden, activations=activations, **shared, **members[m])`` with the member's
+    ``validation_weight`` as the third element of ``validation``.  One ``np.random.default_rng(seed)`` gives the Glorot values
+    of all layers in order, then one permutation per epoch; an epoch has one host read, at which early stopping is decided per
+    member - snapshot on improvement, freeze when out of patience.
+
+    ``hidden=()`` is allowed and takes any number of classes ``fit_head`` takes: the one-layer head of more than 64 classes
+    that ``fit_heads`` refuses.  Up to 64 classes it gives ``fit_heads``'s bits.  ``ValueError`` before any device work."""
+    members = list(members)
+    classes, widths, acts, (n, host, dev, t_host), val = check_fit_arguments(
+        embeddings, targets, classes, hidden, activations, loss, optimizer, 1e-3, epochs, batch_size, validation)
+    if validation is not None and len(validation) != 2:
+        raise ValueError("validation must be (embeddings, targets): a member's weights of those rows are its validation_weight")
+    checked = check_members(members, classes, loss, epochs, t_host, val[0] if val is not None else None)
+    rng = np.random.default_rng(seed)
+    layers = glorot_layers(rng, widths, acts)
+    bank = TrainerStackBank([layers] * len(members), loss, optimizer, checked[0][2][0], max_batch=int(batch_size),
+                            device=device if device is not None else (dev.device.index if dev is not None else None))
+    return _fit_members(bank, checked, rng, (n, host, dev, t_host), val, validation is not None and validation[0] is embeddings,
+                        int(epochs), int(batch_size), classes, lambda m: [bank.read(m, l) + (a,) for l, a in enumerate(acts)])
+
+
+def _fit_members(bank, checked, rng, data, val, validation_is_training, epochs, batch, classes, read_layers) -> List[FitResult]:
+    """The epochs of ``fit_heads`` and ``fit_stacks``: ``bank`` (a ``TrainerBank`` or ``TrainerStackBank``, closed here) holds
+    the members at their initial values, ``checked`` is ``check_members``' result, ``rng`` the generator behind the initial
+    values, ``data`` and ``val`` are ``check_fit_arguments``', and ``read_layers(m)`` gives member m's layers for its head."""
+    import torch
+    n, host, dev, t_host = data
+    M = len(checked)
     rates = [c[2] for c in checked]
     stops = [c[4] for c in checked]
-    bank = TrainerBank([(kernel, bias)] * M, loss, optimizer, rates[0][0], max_batch=batch,
-                       device=device if device is not None else (dev.device.index if dev is not None else None))
     best_epoch: List[Optional[int]] = [None] * M
     stopped_epoch: List[Optional[int]] = [None] * M
     try:
@@ -788,14 +904,14 @@ def fit_heads(embeddings, targets, classes, members, *, hidden=(), activations=(
             Wt = stacked([c[0] for c in checked], n)
             w_epoch = VW = None
             if val is not None:
-                VX = X if validation[0] is embeddings else resident(val[1], val[2])
+                VX = X if validation_is_training else resident(val[1], val[2])
                 VT = torch.from_numpy(val[3]).to(bank.device)
                 VW = stacked([c[1] for c in checked], val[0])
                 val_words = torch.zeros(M, dtype=torch.float32, device=bank.device)
                 val_sums = torch.zeros(M, dtype=torch.float64, device=bank.device)
             histories: List[Dict[str, List[float]]] = [{"loss": [], **({"val_loss": []} if val is not None else {})} for _ in range(M)]
             best, waited, active = [float("inf")] * M, [0] * M, [True] * M
-            for epoch in range(int(epochs)):
+            for epoch in range(epochs):
                 for m in range(M):
                     if active[m]:
                         bank.set_learning_rate(m, rates[m][epoch])
@@ -838,7 +954,7 @@ def fit_heads(embeddings, targets, classes, members, *, hidden=(), activations=(
             for m in range(M):
                 if stops[m] is not None and stops[m][2] and best_epoch[m] is not None and best_epoch[m] != stopped_epoch[m]:
                     bank.restore(m)
-                out.append(FitResult(weights.HeadWeights([bank.read(m) + (acts[0],)], classes, source="fit_head"), histories[m],
+                out.append(FitResult(weights.HeadWeights(read_layers(m), classes, source="fit_head"), histories[m],
                                      best_epoch[m], stopped_epoch[m]))
     finally:
         bank.close()
@@ -1040,19 +1156,43 @@ def cross_validate_head(embeddings, targets, classes, *, folds=None, groups=None
 
     The result's ``entries[g]`` hold ``oof_logits``, the K ``FitResult``, ``fold_best`` and ``metrics(class_name)``; ``best`` is
     the entry with the lowest mean ``fold_best``.  The final model stays the caller's own ``fit_head`` on all rows with
-    ``grid[best]``.  Hidden layers are outside the bank and not offered here."""
+    ``grid[best]``.  Hidden layers are outside the bank and not offered here: ``cross_validate_stack`` takes them."""
+    return _cross_validate(embeddings, targets, classes, (), (), folds, groups, fold_of_row, grid, loss, optimizer, epochs, batch_size,
+                           seed, device, shared, fit_heads, lambda fits, **kw: TrainerBank([f.head.layers[0][:2] for f in fits], **kw))
+
+
+def cross_validate_stack(embeddings, targets, classes, *, hidden=(), activations=(), folds=None, groups=None, fold_of_row=None,
+                         grid=({},), loss="categorical", optimizer="adam", epochs=10, batch_size=256, seed=0, device=None,
+                         **shared) -> CrossValidation:
+    """``cross_validate_head`` for heads of any shape ``fit_head`` takes: ``1024 -> hidden... -> len(classes)`` with
+    ``activations`` on the hidden layers (``hidden=()``: one layer of any number of classes).  Folds, grid, ``shared``, checks
+    and the result are ``cross_validate_head``'s; every (fold, grid entry) is fitted in one pass by ``fit_stacks`` and is, bit
+    for bit, the ``fit_head(..., hidden=hidden, activations=activations)`` call ``fold_members`` describes; the out-of-fold
+    logits come from one forward pass of a ``TrainerStackBank`` loaded with the fitted members.  The final model stays the
+    caller's own ``fit_head`` on all rows with ``grid[best]`` and the same shape.  ``ValueError`` before any device work, a grid
+    entry's with ``grid[g]:`` in front."""
+    def fit(*args, **kw):
+        return fit_stacks(*args, hidden=hidden, activations=activations, **kw)
+    return _cross_validate(embeddings, targets, classes, hidden, activations, folds, groups, fold_of_row, grid, loss, optimizer, epochs,
+                           batch_size, seed, device, shared, fit, lambda fits, **kw: TrainerStackBank([f.head.layers for f in fits], **kw))
+
+
+def _cross_validate(embeddings, targets, classes, hidden, activations, folds, groups, fold_of_row, grid, loss, optimizer, epochs,
+                    batch_size, seed, device, shared, fit, bank_of) -> CrossValidation:
+    """The body of ``cross_validate_head`` and ``cross_validate_stack``: ``fit`` is ``fit_heads`` or ``fit_stacks`` with the
+    shape bound, ``bank_of(fits, ...)`` the bank that holds the fitted members for the out-of-fold forward pass."""
     unknown = sorted(set(shared) - set(MEMBER_KEYS[:-1]))
     if unknown:
         raise ValueError(f"unknown arguments {unknown}")
     classes, widths, acts, (n, host, dev, t_host), _ = check_fit_arguments(
-        embeddings, targets, classes, (), (), loss, optimizer, 1e-3, epochs, batch_size, None)
+        embeddings, targets, classes, hidden, activations, loss, optimizer, 1e-3, epochs, batch_size, None)
     fold_of_row, k, grid, members = check_cross_validation(t_host, classes, loss, folds, groups, fold_of_row, grid, seed, shared)
-    fits = fit_heads(embeddings, targets, classes, members, loss=loss, optimizer=optimizer, epochs=epochs, batch_size=batch_size,
-                     seed=seed, validation=(embeddings, targets), device=device)
+    fits = fit(embeddings, targets, classes, members, loss=loss, optimizer=optimizer, epochs=epochs, batch_size=batch_size,
+               seed=seed, validation=(embeddings, targets), device=device)
     import torch
     batch = int(batch_size)
-    bank = TrainerBank([f.head.layers[0][:2] for f in fits], loss, optimizer, max_batch=batch,
-                       device=device if device is not None else (dev.device.index if dev is not None else None))
+    bank = bank_of(fits, loss=loss, optimizer=optimizer, max_batch=batch,
+                   device=device if device is not None else (dev.device.index if dev is not None else None))
     try:
         with torch.cuda.device(bank.device):
             X = (dev if dev is not None else torch.from_numpy(host)).to(bank.device)

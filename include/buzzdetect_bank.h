@@ -36,8 +36,9 @@
  * multiple of 4.  The learning rate and decay of a step are those set when it is enqueued: they travel by value in its
  * launches.  A handle is not thread-safe.
  *
- * Out of scope: hidden layers in a bank; members that differ in C, loss, optimizer kind or batch order; more than one device;
- * and everything buzzdetect_train.h lists as out of scope.
+ * Out of scope: hidden layers and more than BD_TRAIN_FUSED_MAX_WIDTH outputs in this bank (buzzdetect_stackbank.h holds whole
+ * stacks, with the same contract); members that differ in C, loss, optimizer kind or batch order; more than one device; and
+ * everything buzzdetect_train.h lists as out of scope.
  */
 #ifndef BUZZDETECT_BANK_H
 #define BUZZDETECT_BANK_H
