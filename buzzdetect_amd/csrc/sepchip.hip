@@ -17,7 +17,9 @@
 //     (13 x 12.1 KB = 157.6 KB); stages 13-15 stay PENDING in the registers of waves 5-7 (48 packed dwords each) until stages
 //     0-2 have been consumed, and then take their slots.  Four workgroup barriers per layer (tile published / slots 0-2
 //     free / pending published / tile consumed) instead of one per stage: between them the eight waves drift freely and two
-//     matrix waves per SIMD cover each other's LDS and L2 latency.
+//     matrix waves per SIMD cover each other's LDS and L2 latency.  Round 9: the older wave of a SIMD (0-3) takes the
+//     tile-consumed barrier behind its depthwise, the younger one (4-7), which leaves the K loop last, in front of it: the
+//     older waves publish while the younger ones compute.
 //   * Weights as in the 12-wave kernel of rounds 2-5: B fragments straight from the fragment-ordered copy (L2) into registers, two k16 steps
 //     ahead.
 //
@@ -282,6 +284,7 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         const __amdgpu_buffer_rsrc_t taps = CHIP_TAPS_RSRC(taps_w);
         const __amdgpu_buffer_rsrc_t pur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pu), 0, K * 4, 0x00020000);
         const __amdgpu_buffer_rsrc_t pbr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pb), 0, K * 4, 0x00020000);
+        if (wc >= 4) __syncthreads();             // (the ring-free barrier of the younger waves: see below)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int st = j ? wc + 8 : wc;       // stage of the next layer = column block of this one
@@ -314,8 +317,11 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         // The barrier that frees the ring stands HERE, behind the depthwise: the two matrix waves of a SIMD do not finish a
         // layer's K loop together (the older one gets the pipe first), and everything above needs only the wave's own
         // accumulators - so the early wave's vector work runs beside the late wave's last MFMAs, and the late wave's has the
-        // vector unit to itself, instead of both waiting and then sharing it.
-        __syncthreads();                          // every wave has read every stage: the ring is free for this layer's tile
+        // vector unit to itself, instead of both waiting and then sharing it.  That is so for the OLDER wave of a SIMD (waves
+        // 0-3).  The younger one (waves 4-7) leaves the K loop last: it takes its barrier - one per wave either way, in a
+        // wave-uniform branch - in front of its depthwise, so that the older waves publish while it computes instead of all
+        // eight publishing together behind it.  Correct whichever wave is late in fact.
+        if (wc < 4) __syncthreads();              // every wave has read every stage: the ring is free for this layer's tile
         CHIP_TS()
         CHIP_PUBLISH()
     };

@@ -23,6 +23,9 @@
 // Arithmetic per element is that of the kernels it replaces (pw_res_kernel, sep_ws_kernel<NDW = 1>): products lo*hi, hi*lo,
 // hi*hi per k16 step in ascending order, relu(fma(acc, u, b)), depthwise = shift then taps in row-major order with fmaf, the
 // range guard's maximum over everything that is split.  Taps outside the map are skipped or multiply a zero (sepchip.hip).
+// Round 9: a wave reads its share of the window (the f32 depthwise-5 output) as one contiguous 6 KB run, six 16-byte loads per
+// lane where 24 dword loads stood, and a lane - now four channels of one position - splits them and writes hi and lo as one
+// 8-byte LDS write each (12 per lane and window, 48 two-byte writes before).  The LDS image and every bit are unchanged.
 #include "bd_device.h"
 
 #include <type_traits>
@@ -74,6 +77,10 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
     }
     // publisher (96-row stages): lane (k = frow, fh) writes rows 48 fh + rl; byte offset of k in a row whose key is m = wb0 ^ (m << 4)
     const int wb0 = fh * (48 * 64 + 64) + ((frow >> 3) << 4) + 2 * (frow & 7);
+    // publisher of A5 (lane = channels 4 frow .. + 3 of a position whose x & 1 is fh): stage frow >> 3, slot (frow & 7) >> 1 (bits
+    // 4-5, clear in everything else here: the key is XORed in per row), 8 bytes per half slot, + fh rows
+    const int wb5 = (frow >> 3) * kSlotA + fh * 64 + (((frow & 7) >> 1) << 4) + 8 * (frow & 1);
+    static_assert((kSlotA & 0x70) == 0 && kHalfA % 8 == 0, "the slot bits of wb5 are its own; 8-byte writes");
     // publisher (layer 7's 48-row stages): rows 24 half + 4 oy + 2 fh + j
     const int wb7 = fh * 128 + ((frow >> 3) << 4) + 2 * (frow & 7);
     // reader: lane (frow, fh) supplies A[row 32 i + frow][k = 16 s + 8 fh ..]: slot (2 s + fh) ^ key, key = (frow >> 2) & 3
@@ -129,18 +136,15 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
         IN2[7][c] = v2f{c == 0 ? LH[6] : c == 5 ? RH[6] : EV[6][c - 1], 0.0f};                            \
     }
 
-    // this wave's share of a window's input (the depthwise-5 output): stage wc & 3, rows 24 (wc >> 2) .. + 23 of the lane's half.
-    // Requested a layer ahead of its use: the loads of window n + 1 fly behind the depthwise 7 (and pointwise 7) of window n.
-    float vin[24];
+    // this wave's share of a window's input (the depthwise-5 output, [96 positions][128 channels] f32): positions 12 wc .. + 11,
+    // one contiguous 6 KB run, at 16 bytes per lane - load t brings position 12 wc + 2 t + fh, channels 4 frow .. + 3.  The
+    // resource covers exactly this window.  Requested a layer ahead of its use: the loads of window n + 1 fly behind the
+    // depthwise 7 (and pointwise 7) of window n.
+    v4f vin[6];
     auto fetch_window = [&](int win) {
         const __amdgpu_buffer_rsrc_t xr = MID_RSRC(X + (size_t)win * 96 * 128, 96 * 128 * 4);
-        const int st = wc & 3, rl0 = 24 * (wc >> 2);
-        const unsigned vo = (4u * fh * 128) * 4 + c4;
 #pragma unroll
-        for (int t = 0; t < 24; ++t) {
-            const int rl = rl0 + t;                                        // (wave-uniform; map row rl >> 2, column 4 fh + (rl & 3))
-            vin[t] = MID_LD32(xr, vo, ((8 * (rl >> 2) + (rl & 3)) * 128 + 32 * st) * 4);
-        }
+        for (int t = 0; t < 6; ++t) vin[t] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xr, lane16, (6 * wc + t) * 1024, 0));
     };
     // layer 7's B fragments (column tiles wc, wc + 8), a ring of three k16 steps; the first two are requested by the window that
     // completes A7, in front of its last barrier
@@ -150,24 +154,22 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
     auto window_to_a7 = [&](auto half_c, auto last_c, int win, int win_next) {
         constexpr int HALF = decltype(half_c)::value;
         constexpr bool LAST = decltype(last_c)::value;     // layer 7 runs behind this window
-        // ---- A5: split, stage wc & 3 of the ring
+        // ---- A5: split; a lane's four channels are 8 contiguous bytes of one 16-byte slot of stage frow >> 3, hi and lo one
+        // 8-byte write each.  Position 12 wc + 2 t + fh = (y, x) is row 48 (x >> 2) + 4 y + (x & 3): all of it but the + fh is
+        // wave-uniform, and so is the row's key (row >> 2) & 3 = y & 3
         {
-            const int st = wc & 3;
-            int wbl = wb0;
+            int wbl = wb5;
             asm volatile("" : "+v"(wbl));
-            char* const slot = sm + st * kSlotA;
-            if (wc < 4) {
 #pragma unroll
-                for (int t = 0; t < 24; ++t) {
-                    MID_SPLIT(vin[t], pk)
-                    MID_PUT(slot, t, pk)
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < 24; ++t) {
-                    MID_SPLIT(vin[t], pk)
-                    MID_PUT(slot, 24 + t, pk)
-                }
+            for (int t = 0; t < 6; ++t) {
+                const int pe = 12 * wc + 2 * t;                                // (even: x & 1 = fh)
+                const int y = pe >> 3, xh = (pe >> 2) & 1;
+                rmax = range_of(rmax, vin[t]);
+                f16x4 hi, lo;
+                split_f16(vin[t], hi, lo);
+                char* const p_ = sm + (wbl ^ ((y & 3) << 4)) + (48 * xh + 4 * y + (pe & 2)) * 64 + xh * 64;
+                *reinterpret_cast<f16x4*>(p_) = hi;
+                *reinterpret_cast<f16x4*>(p_ + kHalfA) = lo;
             }
         }
         // (the B fragments of a K loop's first two k16 steps are requested in FRONT of the barrier that publishes its A operand:
