@@ -179,6 +179,24 @@ HEAD_PROTOTYPES = {
     "bd_head_outputs": (C.c_int, [C.c_void_p]),
 }
 
+HEADSET_ABI_VERSION = 1
+HEADSET_MAX_MEMBERS = 64
+HEADSET_ROW = 2048                  # floats per window the hidden activations of one depth share (each width rounded up to 32)
+
+
+class bd_headset_member(C.Structure):
+    _fields_ = [("layers", C.POINTER(bd_head_layer)), ("n_layers", C.c_int32), ("reserved", C.c_int32)]
+
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_headset.h
+HEADSET_PROTOTYPES = {
+    "bd_headset_abi_version": (C.c_int, []),
+    "bd_headset_attach": (C.c_int, [C.c_void_p, C.POINTER(bd_headset_member), C.c_int32]),
+    "bd_headset_members": (C.c_int, [C.c_void_p]),
+    "bd_headset_outputs": (C.c_int, [C.c_void_p]),
+    "bd_headset_columns": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+}
+
 ANYRATE_ABI_VERSION = 1
 
 # name -> (restype, argtypes); one entry per prototype in include/buzzdetect_anyrate.h
@@ -341,7 +359,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             raise RuntimeError(f"{path} is older than its sources and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
-            + list(HEAD_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
+            + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
@@ -354,6 +372,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: PCM ABI version {lib.bd_pcm_abi_version()} != {PCM_ABI_VERSION}; rebuild")
     if lib.bd_head_abi_version() != HEAD_ABI_VERSION:
         raise RuntimeError(f"{path}: head ABI version {lib.bd_head_abi_version()} != {HEAD_ABI_VERSION}; rebuild")
+    if lib.bd_headset_abi_version() != HEADSET_ABI_VERSION:
+        raise RuntimeError(f"{path}: head-set ABI version {lib.bd_headset_abi_version()} != {HEADSET_ABI_VERSION}; rebuild")
     if lib.bd_anyrate_abi_version() != ANYRATE_ABI_VERSION:
         raise RuntimeError(f"{path}: any-ratio ABI version {lib.bd_anyrate_abi_version()} != {ANYRATE_ABI_VERSION}; rebuild")
     if lib.bd_train_abi_version() != TRAIN_ABI_VERSION:

@@ -23,7 +23,7 @@ import re
 from typing import List, Optional
 
 from . import framing, results, sharding
-from .pipeline import FILE_SIZE_MINIMUM, FileJob, Pipeline, Report
+from .pipeline import FILE_SIZE_MINIMUM, FileJob, Member, MemberFile, Pipeline, Report
 from .pipeline import log as _log
 from .wavio import WavTrack  # noqa: F401  (re-exported: the streamer's reader)
 
@@ -77,7 +77,21 @@ def analyze(modelname: str = "model_general_v3", classes_out="all", precision: O
     analysis early - every queue is released, the report comes back with ``end_reason == "interrupted"`` and the partial
     result files are left for the next run to resume; ``verbosity_print`` / ``verbosity_log`` / ``log_progress`` attach
     the reference's console and ``<dir_out>/<timestamp>.log`` handlers to logger ``buzzdetect`` for the duration of the
-    call (None: leave logging to the caller); ``analyzers_cpu`` is accepted and ignored - this engine has no CPU path."""
+    call (None: leave logging to the caller); ``analyzers_cpu`` is accepted and ignored - this engine has no CPU path.
+
+    Several models in one pass: ``modelname`` a list or tuple of names.  Every recording is read, decoded, resampled and
+    embedded ONCE (a set of heads behind one embedder pass, include/buzzdetect_headset.h) and one result tree is written per
+    model: ``models/<name>/output`` each with ``dir_out=None``, else ``<dir_out>/<name>/``.  Every tree is what
+    ``analyze(name, dir_out=that folder)`` alone writes, byte for byte, under that model's own manifest, classes,
+    ``digits_results`` and threshold (``precision`` is looked up in each model's own metrics), so a later run with one model
+    resumes or accepts a tree written here and the other way round.  A ``classes_out`` list applies to every model; one that
+    lacks a name raises ``ValueError`` naming the model, before anything is written.  ``engine`` / ``engines`` must then carry
+    the same models in the same order; ``gather_logits`` takes one model.  The log file goes to ``dir_out`` if given, else to the
+    first model's folder.  The report counts what was embedded: windows, chunks and seconds once per chunk, not once per model."""
+    if isinstance(modelname, (list, tuple)):
+        return _analyze_set(list(modelname), classes_out, precision, framehop_prop, chunklength, dir_audio, dir_out, embeddername,
+                            engine, rank, world_size, analyzers_gpu, n_streamers, engines, gather_logits, analyzers_cpu,
+                            stream_buffer_depth, verbosity_print, verbosity_log, log_progress, event_stopanalysis, dir_models)
     from .engine import HipEngine, hop_samples, patch_step   # device code is only needed once there is work to do
 
     dist = None
@@ -151,6 +165,8 @@ def _analyze(modelname, classes_out, precision, framehop_prop, chunklength, dir_
     if engines:
         engine = None
     probe = engine or (engines[0] if engines else None)
+    if getattr(probe, "members", None):
+        raise ValueError(f"engine= / engines= carry a set of heads ({list(probe.members)}); name the same models as a list")
     # what the reference takes from the model (config_model.json / BaseModel): classes, digits_results, the embedder's name
     head = getattr(probe, "head", None) if probe is not None else weights.load_head(modelname, dir_models)
     if head is None:                                   # an engine without a classifier: the named model's settings
@@ -222,6 +238,140 @@ def _analyze(modelname, classes_out, precision, framehop_prop, chunklength, dir_
     for ident in sorted(conflicting):
         report.messages.append(f"conflicting names, skipped: {ident}")
     return report
+
+
+def member_dirs(names, dir_out: Optional[str]) -> dict:
+    """Where each model of a set writes: its usual ``models/<name>/output``, or ``<dir_out>/<name>``."""
+    return {n: os.path.join(dir_out, n) if dir_out else os.path.join("models", n, "output") for n in names}
+
+
+def set_members(heads: dict, classes_out, precision) -> List[Member]:
+    """The writer's view of a set of heads (host only): every model's columns and its own classes, ``digits_results`` and
+    threshold.  ``ValueError``, naming the model, where a ``classes_out`` list asks for a class the model does not have (the
+    reference's format_activations refuses the same, src/write/formatting.py)."""
+    from . import weights
+    columns = weights.check_head_set(heads)
+    members = []
+    for name, head in heads.items():
+        keep = list(head.classes) if classes_out == "all" else list(classes_out)
+        unknown = [c for c in keep if c not in head.classes]
+        if unknown:
+            raise ValueError(f"model {name!r} has no class {', '.join(repr(c) for c in unknown)} (classes_out)")
+        threshold = None if precision is None else results.threshold_for_precision(name, precision,
+                                                                                     metrics_path=head.metrics_path)
+        members.append(Member(name, columns[name], list(head.classes), keep, head.digits_results, threshold))
+    return members
+
+
+def set_jobs(files, members: List[Member], dirs: dict) -> List[FileJob]:
+    """One job per recording ``(path, ident)``, naming every member's result file; the planner drops the finished ones and
+    splits the job where the members' chunk lists differ (``Pipeline.plan``)."""
+    jobs = []
+    for path, ident in files:
+        outputs = [MemberFile(k, results.ResultFile(os.path.join(dirs[m.name], ident))) for k, m in enumerate(members)]
+        jobs.append(FileJob(path=path, ident=ident, shortpath=ident + os.path.splitext(path)[1], rf=outputs[0].rf, outputs=outputs))
+    return jobs
+
+
+def _analyze_set(names, classes_out, precision, framehop_prop, chunklength, dir_audio, dir_out, embeddername, engine, rank,
+                 world_size, analyzers_gpu, n_streamers, engines, gather_logits, analyzers_cpu, stream_buffer_depth,
+                 verbosity_print, verbosity_log, log_progress, event_stopanalysis, dir_models) -> AnalyzeReport:
+    """analyze() with a list of models: the arguments are checked on the host, then one pipeline feeds engines that carry the
+    set and a writer that appends every chunk's rows to each model's own tree."""
+    from . import weights
+    if gather_logits:
+        raise ValueError("gather_logits takes one model, not a list of them")
+    if engines:
+        engine = None
+    probe = engine or (engines[0] if engines else None)
+    for e in ([engine] if engine is not None else list(engines or [])):
+        if list(getattr(e, "members", None) or []) != names:
+            raise ValueError(f"engine= / engines= must carry the models {names} as a set of heads, in this order; this one carries "
+                             f"{list(getattr(e, 'members', None) or []) or getattr(getattr(e, 'head', None), 'source', 'one head')}")
+    heads = dict(probe.members) if probe is not None else weights.load_head_set(names, dir_models)
+    members = set_members(heads, classes_out, precision)
+    dirs = member_dirs(names, dir_out)
+
+    dist = None
+    if rank is None or world_size is None:
+        try:
+            import torch.distributed as dist_mod
+            if dist_mod.is_available() and dist_mod.is_initialized():
+                dist = dist_mod
+                rank, world_size = dist.get_rank(), dist.get_world_size()
+        except ImportError:
+            pass
+    rank, world_size = rank or 0, world_size or 1
+    handlers = _attach_log_handlers(dir_out or dirs[names[0]], verbosity_print, verbosity_log, log_progress)
+    try:
+        from .engine import HipEngine, hop_samples, patch_step
+        if analyzers_cpu:
+            _log.debug(f"analyzers_cpu={analyzers_cpu} ignored: the MI355X engine has no CPU path")
+        framelength_s, digits_time = 0.96, 2
+        framehop_s = framelength_s * framehop_prop
+        chunklength = framing.round_chunklength(chunklength, framelength_s, digits_time)
+        if embeddername is None:
+            embeddername = next(iter(heads.values())).embeddername
+
+        # every model's folder is locked to that model's own settings, exactly as a run with it alone locks it
+        manifests = {m.name: results.build_manifest(m.name, framehop_prop, precision, m.classes_out) for m in members}
+
+        def check_manifests():
+            for name, manifest in manifests.items():
+                ok, msg = results.check_or_write_manifest(dirs[name], manifest)
+                if not ok:
+                    return msg
+            return None
+        msg = check_manifests() if rank == 0 else None
+        if dist is not None and world_size > 1:
+            dist.barrier()
+        if rank != 0:
+            msg = check_manifests()
+        if msg:
+            raise RuntimeError(msg)
+
+        paths = search_audio(dir_audio)
+        idents = [build_ident(p, dir_audio) for p in paths]
+        conflicting = {i for i in idents if idents.count(i) > 1}
+        todo = [(p, i) for p, i in zip(paths, idents) if i not in conflicting]
+        mine = [todo[k] for k in sharding.shard_indices(len(todo), rank, world_size)]
+        if probe is None:
+            probe = HipEngine(embeddername=embeddername, heads=heads)
+        device_index = probe.device_index
+        if engine is not None:
+            analyzers, make_engine = 1, (lambda: engine)
+        elif engines:
+            analyzers, pool = len(engines), list(engines)
+            pool_lock = __import__("threading").Lock()
+
+            def make_engine():
+                with pool_lock:
+                    return pool.pop()
+        else:
+            analyzers = max(1, int(analyzers_gpu))
+            first = [probe]
+
+            def make_engine():        # the probe engine serves the first analyzer thread; the others build their own
+                if first:
+                    return first.pop()
+                return HipEngine(embeddername=embeddername, heads=heads, device=device_index)
+
+        readers = n_streamers if n_streamers else STREAMERS_PER_ANALYZER * analyzers
+        pipe = Pipeline(make_engine=make_engine, classes=probe.classes, framehop_s=framehop_s, hop=hop_samples(framehop_s),
+                        step=patch_step(framehop_s), chunklength=chunklength, framelength_s=framelength_s,
+                        digits_time=digits_time, digits_results=members[0].digits_results, classes_out="all", threshold=None,
+                        readers=readers, analyzers=analyzers, stop_event=event_stopanalysis,
+                        stream_buffer_depth=stream_buffer_depth, device=probe.device,
+                        resample_quality=getattr(probe, "resample_quality", 1), members=members)
+        report = pipe.run(set_jobs(mine, members, dirs))
+        report.files_total = len(todo)
+        for ident in sorted(conflicting):
+            report.messages.append(f"conflicting names, skipped: {ident}")
+        return report
+    finally:
+        for h in handlers:
+            _log.removeHandler(h)
+            h.close()
 
 
 def gather_plan(todo, dir_out: str, hop: int, step: int, chunklength: float) -> list:

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/buzzdetect_hip.h"
@@ -251,5 +252,43 @@ void dense_pack_weights(const float* kernel, int k, int n, float* dst);      // 
 // C[windows][ldc] (columns < n) = act(A[windows][lda] (columns < k) W + b); lda >= round_up(k, 32), A != C
 void launch_dense(const float* A, int lda, int windows, const DenseLayer& L, float* C, int ldc, hipStream_t stream);
 void launch_softmax_rows(const float* x, int ldx, float* y, int windows, int n, hipStream_t stream);  // x [windows][ldx] -> y [windows][n]
+
+}  // namespace bd
+
+struct bd_headset_member;
+
+namespace bd {
+
+// ---- headset.hip ----
+// A set of heads behind one embedder pass (include/buzzdetect_headset.h).  Scratch per window: kHeadSetRegions rows of
+// kHeadSetRow floats - two (ping, pong) take the hidden activations of every member, depth by depth, each layer in its own
+// 32-aligned column block; the third takes the last layers that stand in front of a softmax, packed like the logits.
+constexpr int kHeadSetRow = 2048;
+constexpr int kHeadSetRegions = 3;
+struct HeadSet {
+    int members = 0, outputs = 0;
+    std::vector<int> first, count;           // per member: its columns of the logits
+    char* dev = nullptr;                     // one allocation: packed kernels, biases, descriptors, tile tables
+    struct Depth {
+        const void* layers;                  // device, SetLayer[]: the layers of the stack-route members at this depth
+        const void* tiles;                   // device, SetTile[n_tiles]: 64-column workgroup tile -> (layer, tile of the layer)
+        int n_tiles;
+    };
+    std::vector<Depth> depths;
+    const void* softmax = nullptr;           // device, SetSoftmax[n_softmax]
+    int n_softmax = 0;
+    const float* fused_wt = nullptr;         // device, [n_fused][1024]: the classes of the fused-route members, concatenated
+    const float* fused_b = nullptr;          // [n_fused]
+    const int* fused_col = nullptr;          // [n_fused]: class -> column of the logits
+    int n_fused = 0;
+};
+// Checks the limits, then uploads (synchronous).  BD_OK, or BD_EINVAL / BD_EHIP with *err set; *out is written on success only.
+int headset_build(const bd_headset_member* members, int n_members, HeadSet* out, std::string* err);
+void headset_free(HeadSet* set);
+// scratch = [kHeadSetRegions][windows][kHeadSetRow]
+void launch_dense_set(const HeadSet& set, int depth, const float* pooled, float* scratch, float* logits, int windows,
+                      hipStream_t stream);
+void launch_softmax_set(const HeadSet& set, const float* scratch, float* logits, int windows, hipStream_t stream);
+void launch_head_set(const HeadSet& set, const float* pooled, float* logits, int windows, hipStream_t stream);
 
 }  // namespace bd

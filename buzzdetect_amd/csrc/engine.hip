@@ -15,6 +15,7 @@
 
 #include "../../include/buzzdetect_anyrate.h"
 #include "../../include/buzzdetect_head.h"
+#include "../../include/buzzdetect_headset.h"
 
 namespace {
 
@@ -83,6 +84,8 @@ struct bd_engine {
     // a dense stack in place of that head (bd_head_attach): n_classes is then its last width
     std::vector<bd::DenseLayer> stack;
     float* d_stack = nullptr;         // one allocation for the stack's packed kernels and biases
+    // or a set of heads (bd_headset_attach, headset.hip): n_classes is then the sum of the members' last widths
+    bd::HeadSet set;
     // resampler: the filters of every (up, down) pair used so far, kept on the device until bd_destroy (nothing is
     // freed or re-uploaded on a rate change: hipFree would synchronise the device under the caller's streams)
     struct Taps {
@@ -627,6 +630,7 @@ int bd_destroy(bd_handle h) {
     }
     if (h->d_amax) (void)hipFree(h->d_amax);
     if (h->d_stack) (void)hipFree(h->d_stack);
+    bd::headset_free(&h->set);
     delete h;
     return BD_OK;
 }
@@ -994,9 +998,24 @@ int stack_head(Group& g, const float* pooled, float* scratch) {
     return BD_OK;
 }
 
+static_assert(BD_EMBEDDING_SIZE + bd::kHeadSetRegions * bd::kHeadSetRow <= kFloatsB, "pooled embeddings + the scratch of a set of heads fit either buffer");
+
+// The attached set of heads (headset.hip) on pooled = [gw][1024]: one launch per depth of its deepest stack, one softmax row
+// pass, one launch for the members of the fused kind - whatever the number of members; scratch = kHeadSetRegions *
+// kHeadSetRow floats per window.  All in slot 28
+int set_head(Group& g, const float* pooled, float* scratch) {
+    const bd::HeadSet& set = g.e->set;
+    for (size_t d = 0; d < set.depths.size(); ++d)
+        g.launch(28, [&] { bd::launch_dense_set(set, (int)d, pooled, scratch, g.logits, g.gw, g.stream); });
+    if (set.n_softmax) g.launch(28, [&] { bd::launch_softmax_set(set, scratch, g.logits, g.gw, g.stream); });
+    if (set.n_fused) g.launch(28, [&] { bd::launch_head_set(set, pooled, g.logits, g.gw, g.stream); });
+    return BD_OK;
+}
+
 // The dense head on the embeddings a tail kernel pooled (into the embeddings or b: a is free by now)
 int head(Group& g, const float* pooled) {
     if (!g.logits) return BD_OK;
+    if (g.e->set.members) return set_head(g, pooled, g.a);
     if (!g.e->stack.empty()) return stack_head(g, pooled, g.a);
     g.launch(28, [&] { bd::launch_head(pooled, g.gw, g.e->head_wt, g.e->head_b, g.e->n_classes, g.logits, g.stream); });
     return BD_OK;
@@ -1022,10 +1041,12 @@ int walk_layers(Group& g, int from, bool dw_done, int stop_stage) {
         pointwise(g, l);
         dw_done = false;
     }
-    if (stop_stage < 0 && !g.e->stack.empty() && g.logits) {
-        // pool alone (a -> the embeddings, or the front of b: the last 1x1 convolution has read b), then the stack behind it
+    if (stop_stage < 0 && (!g.e->stack.empty() || g.e->set.members) && g.logits) {
+        // pool alone (a -> the embeddings, or the front of b: the last 1x1 convolution has read b), then the stack (or the set
+        // of heads) behind it
         float* const pooled = g.emb ? g.emb : g.b;
         g.launch(28, [&] { bd::launch_pool_head(g.a, g.gw, nullptr, nullptr, 0, pooled, nullptr, g.stream); });
+        if (g.e->set.members) return set_head(g, pooled, g.b + (size_t)g.gw * BD_EMBEDDING_SIZE);
         return stack_head(g, pooled, g.b + (size_t)g.gw * BD_EMBEDDING_SIZE);
     }
     if (stop_stage < 0)
@@ -1615,6 +1636,45 @@ int bd_head_attach(bd_handle h, const bd_head_layer* layers, int32_t n_layers) {
     h->d_stack = dev;
     h->stack = std::move(stack);
     h->n_classes = width;
+    return BD_OK;
+}
+
+// ---- the set of heads (header: buzzdetect_headset.h; kernels: headset.hip) ----
+int bd_headset_abi_version(void) { return BD_HEADSET_ABI_VERSION; }
+
+int bd_headset_members(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_headset_members: null handle");
+    return h->set.members;
+}
+
+int bd_headset_outputs(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_headset_outputs: null handle");
+    return h->set.outputs;
+}
+
+int bd_headset_columns(bd_handle h, int32_t member, int32_t* first, int32_t* count) {
+    if (!h || !first || !count) return fail(BD_EINVAL, "bd_headset_columns: null argument");
+    if (member < 0 || member >= h->set.members)
+        return fail(BD_EINVAL, "bd_headset_columns: member " + std::to_string(member) + " outside 0.." +
+                                   std::to_string(h->set.members - 1));
+    *first = h->set.first[member];
+    *count = h->set.count[member];
+    return BD_OK;
+}
+
+int bd_headset_attach(bd_handle h, const bd_headset_member* members, int32_t n_members) {
+    if (!h || !members) return fail(BD_EINVAL, "bd_headset_attach: null argument");
+    if (h->set.members) return fail(BD_EINVAL, "bd_headset_attach: the engine already has a set of heads");
+    if (!h->stack.empty()) return fail(BD_EINVAL, "bd_headset_attach: the engine already has a stack (bd_head_attach)");
+    if (h->n_classes != 0)
+        return fail(BD_EINVAL, "bd_headset_attach: the engine already has a head (create it with n_classes == 0)");
+    BD_HIP(hipSetDevice(h->device));
+    std::string err;
+    bd::HeadSet set;
+    const int rc = bd::headset_build(members, n_members, &set, &err);
+    if (rc != BD_OK) return fail(rc, err);
+    h->set = std::move(set);
+    h->n_classes = h->set.outputs;
     return BD_OK;
 }
 

@@ -19,20 +19,12 @@
 // enough, the instruction's issue interval and its dependent latency both being 64 cycles.  A workgroup is 2 x 2 waves = a
 // 64 x 64 tile, so 1024 windows x 1024 columns are 256 workgroups, one per compute unit.  There is no LDS and no barrier.
 #include "bd_internal.h"
+#include "dense_device.h"
 
 #include "../../include/buzzdetect_head.h"
 
 namespace bd {
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float head_act(float x, int act) {
-    if (act == BD_HEAD_RELU) return fmaxf(x, 0.0f);
-    if (act == BD_HEAD_SIGMOID) return 1.0f / (1.0f + expf(-x));
-    if (act == BD_HEAD_TANH) return tanhf(x);
-    return x;                                   // linear, and softmax (a row pass follows)
-}
 
 __global__ __launch_bounds__(256) void dense_kernel(const float* __restrict__ A, int lda, int W, int K, int n_super,
                                                      const float4* __restrict__ Wf, const float* __restrict__ bias, int N,
@@ -47,54 +39,8 @@ __global__ __launch_bounds__(256) void dense_kernel(const float* __restrict__ A,
     const float* ap = A + (size_t)arow * lda + 4 * half;
     const float4* bp = Wf + (size_t)tc * n_super * 64 + lane;
 
-    float4 a[4], b[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        a[q] = *reinterpret_cast<const float4*>(ap + 8 * q);
-        b[q] = bp[(size_t)q * 64];
-    }
-    v16f acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    for (int s = 0; s < n_super; s += 4) {              // n_super is a multiple of 4
-        float4 an[4], bn[4];
-        const bool more = s + 4 < n_super;
-        if (more) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                an[q] = *reinterpret_cast<const float4*>(ap + 8 * (s + 4 + q));
-                bn[q] = bp[(size_t)(s + 4 + q) * 64];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int k0 = 8 * (s + q) + 4 * half;
-            const float ax = k0 + 0 < K ? a[q].x : 0.0f;
-            const float ay = k0 + 1 < K ? a[q].y : 0.0f;
-            const float az = k0 + 2 < K ? a[q].z : 0.0f;
-            const float aw = k0 + 3 < K ? a[q].w : 0.0f;
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ax, b[q].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ay, b[q].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(az, b[q].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw, b[q].w, acc, 0, 0, 0);
-        }
-        if (more) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                a[q] = an[q];
-                b[q] = bn[q];
-            }
-        }
-    }
-    // accumulator r of lane l is C[32 tr + (r & 3) + 8 (r >> 2) + 4 (l >> 5)][32 tc + (l & 31)]
-    const int col = 32 * tc + (lane & 31);
-    if (col >= N) return;
-    const float bv = bias[col];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = 32 * tr + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (row < W) C[(size_t)row * ldc + col] = head_act(acc[r] + bv, act);
-    }
+    const dense_v16f acc = dense_tile_walk(ap, bp, K, n_super, half);     // (dense_device.h: shared with headset.hip)
+    dense_tile_store(acc, bias, act, tr, tc, W, N, C, ldc, lane);
 }
 
 // softmax over each row of x = [W][ldx] (columns < n) into y = [W][n], out of place (a launch repeated on the same operands gives
@@ -107,15 +53,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     if (row >= W) return;
     const float* p = x + (size_t)row * ldx;
     float* q = y + (size_t)row * n;
-    float m = -INFINITY;
-    for (int c = lane; c < n; c += 64) m = fmaxf(m, p[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    float sum = 0.0f;
-    for (int c = lane; c < n; c += 64) sum += expf(p[c] - m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    for (int c = lane; c < n; c += 64) q[c] = expf(p[c] - m) / sum;
+    softmax_row(p, q, n, lane);
 }
 
 }  // namespace

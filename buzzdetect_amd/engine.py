@@ -225,7 +225,7 @@ class HipEngine:
                  device: Optional[int] = None, embedder_variables: Optional[str] = None,
                  embedder_blob: Optional[np.ndarray] = None, variables_candidates=None,
                  synthetic_weights: Optional[bool] = None, models_dir: Optional[str] = None,
-                 head: Optional["weights.HeadWeights"] = None):
+                 head: Optional["weights.HeadWeights"] = None, heads: Optional[dict] = None):
         """``embedder_blob`` / ``embedder_variables``: the weights / an explicit ``variables.data-00000-of-00001``;
         else ``variables_candidates`` (the embedder plugin passes the places beside itself where the reference keeps its
         SavedModel; default: ``embedders/<name>`` under the working directory and under the packaged overlay), then
@@ -234,8 +234,23 @@ class HipEngine:
         ``modelname`` / ``models_dir``: the classifier, looked up by ``weights.load_head`` (``models/<modelname>`` under the
         working directory, ``$BUZZDETECT_MODELS_DIR``, the packaged overlay; ``models_dir`` replaces them); ``head``: an
         already loaded one.  One linear layer of at most 64 outputs runs fused behind the pool; any other stack is attached
-        with ``bd_head_attach`` and runs one matrix-core launch per layer."""
+        with ``bd_head_attach`` and runs one matrix-core launch per layer.
+        Several models behind one embedder pass (include/buzzdetect_headset.h): ``modelname`` a list or tuple of names, or
+        ``heads = {name: HeadWeights}`` (dict order).  The logits then hold every member's columns side by side
+        (``member_columns``, ``split``), each bit for bit what an engine with that model alone gives; ``members`` is the
+        ordered ``{name: HeadWeights}``, ``classes`` the flat ``"<name>/<class>"`` list, ``head`` None.  An empty list, a name
+        given twice, members on different embedders and a set beyond the library's limits raise ``ValueError`` before any
+        device work (``weights.check_head_set``)."""
         self._handle = C.c_void_p()
+        self.members = None
+        self.member_columns = None
+        if heads is not None and head is not None:
+            raise ValueError("give head= (one model) or heads= (a set), not both")
+        if heads is None and isinstance(modelname, (list, tuple)):
+            heads = weights.load_head_set(modelname, models_dir)
+        if heads is not None:
+            heads = dict(heads)
+            columns = weights.check_head_set(heads)        # host only: the library would refuse the same, later
         self._lib = _lib.load()
         # the weights first (host only): a missing model fails the same way with or without a GPU in the box
         if embedder_blob is None:
@@ -258,7 +273,11 @@ class HipEngine:
         self.classes = None
         self.n_classes = 0
         self.head = None
-        if head is None and modelname is not None:
+        if heads is not None:
+            self.members, self.member_columns = heads, columns
+            self.classes = [f"{name}/{c}" for name, h in heads.items() for c in h.classes]
+            self.n_classes = len(self.classes)
+        elif head is None and modelname is not None:
             head = weights.load_head(modelname, models_dir)
         if head is not None:
             self.head = head
@@ -274,6 +293,8 @@ class HipEngine:
             _lib.check(self._lib.bd_create(C.byref(self._handle), self.device_index, C.byref(w)))
             if head is not None and not head.fused:
                 self._attach_stack(head.layers)
+            if heads is not None:
+                self._attach_set(heads)
         # the handle is not thread-safe (include/buzzdetect_hip.h): every call that takes it goes through this lock, so a
         # writer thread that repeats a flagged chunk cannot interleave with the analyzer thread's next predict
         self._lock = threading.RLock()
@@ -301,6 +322,49 @@ class HipEngine:
         _lib.check(self._lib.bd_head_attach(self._handle, arr, len(layers)))
         if self._lib.bd_head_outputs(self._handle) != self.n_classes:
             raise RuntimeError("bd_head_attach: the attached stack's width differs from the number of classes")
+
+    def _attach_set(self, heads: dict) -> None:
+        """``bd_headset_attach``: every member's layers (the library copies the arrays); the columns it reports are checked
+        against ``member_columns``."""
+        arr = (_lib.bd_headset_member * len(heads))()
+        keep = []
+        for m, head in enumerate(heads.values()):
+            layers = (_lib.bd_head_layer * len(head.layers))()
+            for i, (kernel, bias, activation) in enumerate(head.layers):
+                k = np.ascontiguousarray(kernel, dtype=np.float32)
+                b = np.ascontiguousarray(bias, dtype=np.float32)
+                keep += [k, b]
+                layers[i].kernel = k.ctypes.data_as(C.POINTER(C.c_float))
+                layers[i].bias = b.ctypes.data_as(C.POINTER(C.c_float))
+                layers[i].n_in, layers[i].n_out = k.shape
+                layers[i].activation = _lib.HEAD_ACTIVATIONS[activation]
+            keep.append(layers)
+            arr[m].layers = layers
+            arr[m].n_layers = len(head.layers)
+        _lib.check(self._lib.bd_headset_attach(self._handle, arr, len(heads)))
+        if self._lib.bd_headset_outputs(self._handle) != self.n_classes:
+            raise RuntimeError("bd_headset_attach: the attached set's width differs from the number of classes")
+        first, count = C.c_int32(), C.c_int32()
+        for m, (name, cols) in enumerate(self.member_columns.items()):
+            _lib.check(self._lib.bd_headset_columns(self._handle, m, C.byref(first), C.byref(count)))
+            if (first.value, first.value + count.value) != (cols.start, cols.stop):
+                raise RuntimeError(f"bd_headset_columns: member {name!r} sits at {first.value}..{first.value + count.value}, "
+                                   f"expected {cols.start}..{cols.stop}")
+
+    def split(self, result) -> dict:
+        """``{name: view}`` of a ``predict`` / ``predict_batch`` / ``launch`` result of a set of heads: every member's columns
+        of the rows (a NumPy array, a ``DeviceResult`` or a tensor; device rows are brought to the host once)."""
+        if self.member_columns is None:
+            raise RuntimeError("split() is for an engine with several models (modelname=[...] or heads={...})")
+        if isinstance(result, DeviceResult):
+            rows = result.numpy()
+        elif isinstance(result, torch.Tensor):
+            rows = result.cpu().numpy()
+        else:
+            rows = np.asarray(result)
+        if rows.ndim != 2 or rows.shape[1] != self.n_classes:
+            raise ValueError(f"split() takes [windows, {self.n_classes}] rows, not {tuple(rows.shape)}")
+        return {name: rows[:, cols] for name, cols in self.member_columns.items()}
 
     # ------------------------------------------------------------------ lifecycle
     def close(self) -> None:

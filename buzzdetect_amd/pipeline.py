@@ -72,6 +72,28 @@ class PipelineAborted(Exception):
 
 
 @dataclass
+class Member:
+    """One model of a set of heads (engine.HipEngine(modelname=[...])): its columns of the engine's rows and the settings its
+    result files are written with - its own, as a run with this model alone would take them."""
+    name: str
+    columns: slice
+    classes: List[str]
+    classes_out: object               # a list of this model's classes
+    digits_results: int
+    threshold: Optional[float]
+
+
+@dataclass
+class MemberFile:
+    """One member's result file of one recording, and what the writer keeps for it (FileJob keeps the same for its one file)."""
+    member: int                       # index into Pipeline.members
+    rf: results.ResultFile
+    fresh: bool = True
+    header: bytes = b""
+    bodies: List[Tuple[float, bytes]] = field(default_factory=list)
+
+
+@dataclass
 class FileJob:
     path: str
     ident: str
@@ -85,6 +107,10 @@ class FileJob:
     bad_read: bool = False        # the file ended before its header said it would: said once (handle_bad_read)
     index: int = -1               # position in the run's recording list (gather mode)
     rows: List[Tuple[float, "np.ndarray"]] = field(default_factory=list)  # (chunk start, logits) when a file sink takes the rows
+    # a set of heads: the members this job's chunks are written for, each into its own file (None: one model, `rf`); and,
+    # shared by the jobs the planner makes of ONE recording whose members have different chunks left, how many are unfinished
+    outputs: Optional[List[MemberFile]] = None
+    siblings: Optional[List[int]] = None  # [jobs unfinished, files written]
 
 
 @dataclass
@@ -303,7 +329,7 @@ class Pipeline:
                  threshold: Optional[float], readers: int = 4, analyzers: int = 2, device=None,
                  file_sink: Optional[Callable[[FileJob, List[Tuple[float, "np.ndarray"]]], None]] = None,
                  ignore_partial: bool = False, stop_event=None, stream_buffer_depth: Optional[int] = None,
-                 pin_memory: bool = True, resample_quality: int = 1):
+                 pin_memory: bool = True, resample_quality: int = 1, members: Optional[Sequence[Member]] = None):
         import torch
         self.torch = torch
         self.make_engine = make_engine
@@ -315,6 +341,9 @@ class Pipeline:
         # file_sink: instead of writing result files, hand every finished recording's rows (sorted by chunk start) to this
         # callable from the writer thread (the multi-GPU gather: rank 0 writes what the other ranks computed)
         self.file_sink, self.ignore_partial = file_sink, ignore_partial
+        # members: the engines carry a set of heads; a job with `outputs` is written once per member named there, each with
+        # that member's columns and settings (classes / classes_out / digits_results / threshold above are then not used)
+        self.members = list(members) if members is not None else None
         self.q_files: "queue.Queue" = queue.Queue()
         self.q_units: "queue.Queue" = queue.Queue(maxsize=8 * self.n_readers)
         # chunks buffered between streamers and analyzers: the reference's stream_buffer_depth, by default 2 x streamers
@@ -377,9 +406,8 @@ class Pipeline:
             if message:
                 self.report.messages.append(message)
 
-    def _plan_file(self, job: FileJob) -> None:
-        if job.rf.complete and not self.ignore_partial:     # (gather mode: the plan is rank 0's, this rank just delivers)
-            return self._skip("planner", job, f"Skipping {job.shortpath}; already analyzed")
+    def _open_for_plan(self, job: FileJob):
+        """The size, header and sample-rate rules of the planner: the open track, or None after the skip has been said."""
         if os.path.getsize(job.path) < FILE_SIZE_MINIMUM:
             return self._skip("planner", job, f"Skipping {job.shortpath}; below minimum analyzeable size")
         try:
@@ -391,6 +419,19 @@ class Pipeline:
             track.close()                                   # (outside bd_resample_any's range, buzzdetect_anyrate.h)
             return self._skip("planner", job, f"{job.shortpath}: cannot resample {track.samplerate} Hz to 16000 Hz on the device; skipping",
                               logging.WARNING, f"sample rate {track.samplerate} Hz not supported, skipped: {job.shortpath}")
+        return track
+
+    def plan(self, job: FileJob) -> List[Tuple[FileJob, list]]:
+        """[(job, chunks)] still to analyse of one recording: nothing (the skip has been said), the job with its chunk list, or -
+        for a set of heads whose members have different chunks left - one job per group of members with the same list."""
+        if job.outputs is not None:
+            return self._plan_members(job)
+        if job.rf.complete and not self.ignore_partial:     # (gather mode: the plan is rank 0's, this rank just delivers)
+            self._skip("planner", job, f"Skipping {job.shortpath}; already analyzed")
+            return []
+        track = self._open_for_plan(job)
+        if track is None:
+            return []
         job.fresh = not os.path.exists(job.rf.path_partial)
         if self.ignore_partial:
             chunks = framing.gaps_to_chunklist([(0, track.duration)], self.chunklength)
@@ -398,12 +439,54 @@ class Pipeline:
             chunks = job.rf.pending_chunks(track.duration, self.chunklength, self.framelength_s)
         if not chunks:
             track.close()
-            return self._skip("planner", job, f"Skipping {job.shortpath}; nothing left to analyze")
-        log.info(f"planner: buffering {job.shortpath}")
+            self._skip("planner", job, f"Skipping {job.shortpath}; nothing left to analyze")
+            return []
         job.track = track
-        job.outstanding = len(chunks)                      # known before the first unit is out: no finalisation race
-        for chunk in chunks:
-            self._put(self.q_units, ReadUnit(job, (float(chunk[0]), float(chunk[1]))))
+        return [(job, chunks)]
+
+    def _plan_members(self, job: FileJob) -> List[Tuple[FileJob, list]]:
+        """Resume stays per member: every unfinished member's own result file says which chunks it lacks.  Members with equal
+        lists share one job (the normal case: the recording is read and embedded once); members whose lists differ - a run
+        that was interrupted between two members' appends - get jobs of their own; a finished member is left untouched, and
+        a recording finished for every member is not opened."""
+        unfinished = [mf for mf in job.outputs if not mf.rf.complete]
+        if not unfinished:
+            self._skip("planner", job, f"Skipping {job.shortpath}; already analyzed")
+            return []
+        track = self._open_for_plan(job)
+        if track is None:
+            return []
+        groups: List[Tuple[list, List[MemberFile]]] = []
+        for mf in unfinished:
+            mf.fresh = not os.path.exists(mf.rf.path_partial)
+            chunks = [(float(a), float(b)) for a, b in mf.rf.pending_chunks(track.duration, self.chunklength, self.framelength_s)]
+            if not chunks:
+                continue                                    # (its partial file covered everything: pending_chunks finalised it)
+            for have, mfs in groups:
+                if have == chunks:
+                    mfs.append(mf)
+                    break
+            else:
+                groups.append((chunks, [mf]))
+        if not groups:
+            track.close()
+            self._skip("planner", job, f"Skipping {job.shortpath}; nothing left to analyze")
+            return []
+        siblings = [len(groups), 0]                         # jobs of this recording still open, files they have written
+        out = []
+        for k, (chunks, mfs) in enumerate(groups):
+            j = job if k == 0 else FileJob(path=job.path, ident=job.ident, shortpath=job.shortpath, rf=mfs[0].rf, index=job.index)
+            j.outputs, j.siblings, j.rf = mfs, siblings, mfs[0].rf
+            j.track = track if k == 0 else open_track(job.path)          # (every job closes its own when it is finalised)
+            out.append((j, chunks))
+        return out
+
+    def _plan_file(self, job: FileJob) -> None:
+        for j, chunks in self.plan(job):
+            log.info(f"planner: buffering {j.shortpath}")
+            j.outstanding = len(chunks)                    # known before the first unit is out: no finalisation race
+            for chunk in chunks:
+                self._put(self.q_units, ReadUnit(j, (float(chunk[0]), float(chunk[1]))))
 
     def _rate_supported(self, rate: int) -> bool:
         """bd_anyrate_supported for the quality the engines run (host only: no handle, no device)."""
@@ -732,23 +815,37 @@ class Pipeline:
             with self.lock:
                 self.report.files_done += 1
             return
-        if not os.path.exists(job.rf.path_partial):
+        if job.outputs is not None:                        # a set of heads: every member's file of this job, then the
+            wrote = [self._finalize_file(mf.rf, mf) for mf in job.outputs]       # recording counts once
+            with self.lock:
+                job.siblings[0] -= 1
+                job.siblings[1] += sum(wrote)
+                if job.siblings[0] == 0 and job.siblings[1]:
+                    self.report.files_done += 1
             return
-        if job.fresh and job.bodies:
+        if self._finalize_file(job.rf, job):
+            with self.lock:
+                self.report.files_done += 1
+
+    @staticmethod
+    def _finalize_file(rf: results.ResultFile, kept) -> bool:
+        """kept: the FileJob or MemberFile that holds `fresh`, `header` and `bodies` of this file.  False: nothing was written."""
+        if not os.path.exists(rf.path_partial):
+            return False
+        if kept.fresh and kept.bodies:
             # the reference reads the partial file, sorts by start and writes the complete one (src/write/worker.py:82-86);
             # for a recording this run started from nothing, the same bytes come from the rows kept in memory
-            job.bodies.sort(key=lambda sb: sb[0])
-            tmp = job.rf.path_complete + ".tmp"
+            kept.bodies.sort(key=lambda sb: sb[0])
+            tmp = rf.path_complete + ".tmp"
             with open(tmp, "wb") as f:
-                f.write(job.header)
-                f.writelines(b for _, b in job.bodies)
-            os.replace(tmp, job.rf.path_complete)
-            os.remove(job.rf.path_partial)
+                f.write(kept.header)
+                f.writelines(b for _, b in kept.bodies)
+            os.replace(tmp, rf.path_complete)
+            os.remove(rf.path_partial)
         else:
-            job.rf.finalize()
-        job.bodies = []
-        with self.lock:
-            self.report.files_done += 1
+            rf.finalize()
+        kept.bodies = []
+        return True
 
     def _writer(self) -> None:
         try:
@@ -774,7 +871,24 @@ class Pipeline:
                 for t, n in zip(item.tasks, item.counts):
                     rows = item.host[at:at + n]
                     at += n
-                    if self.file_sink is not None:
+                    if t.job.outputs is not None:          # a set of heads: the chunk's rows once per member of this job
+                        for mf in t.job.outputs:
+                            m = self.members[mf.member]
+                            own = np.ascontiguousarray(rows[:, m.columns])
+                            if m.threshold is None:
+                                head, body = results.activation_csv(own, m.classes, self.framehop_s, self.digits_time, t.chunk[0],
+                                                                    m.classes_out, m.digits_results)
+                            else:
+                                head, body = results.detection_csv(own, m.threshold, m.classes, self.framehop_s,
+                                                                   self.digits_time, t.chunk[0])
+                            t1 = time.perf_counter()
+                            mf.rf.append_text(head, body)
+                            t_io += time.perf_counter() - t1
+                            if mf.fresh:
+                                mf.header = head
+                                mf.bodies.append((t.chunk[0], body))
+                        head = body = None
+                    elif self.file_sink is not None:
                         t.job.rows.append((t.chunk[0], rows.copy()))
                         head = body = None
                     elif self.threshold is None:

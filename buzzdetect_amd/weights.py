@@ -276,6 +276,57 @@ class HeadWeights:
         return len(self.layers) == 1 and self.layers[0][2] == "linear" and self.layers[0][0].shape[1] <= HEAD_FUSED_MAX
 
 
+HEADSET_MAX_MEMBERS = 64    # members of a set of heads (BD_HEADSET_MAX_MEMBERS)
+HEADSET_ROW = 2048          # what the hidden activations of one depth of a set may take together, each width rounded up to 32
+
+
+def load_head_set(names, models_dir: Optional[str] = None) -> "Dict[str, HeadWeights]":
+    """The members of a set of heads by name, in the order given (``load_head`` each): ``{name: HeadWeights}``.  An empty list
+    and a name given twice are refused with ``ValueError`` before anything is read."""
+    names = list(names)
+    if not names:
+        raise ValueError("a set of heads needs at least one model name (the list is empty)")
+    twice = sorted({n for n in names if names.count(n) > 1})
+    if twice:
+        raise ValueError(f"a set of heads names every model once; given twice: {', '.join(twice)}")
+    return {n: load_head(n, models_dir) for n in names}
+
+
+def check_head_set(members: "Dict[str, HeadWeights]") -> "Dict[str, slice]":
+    """What ``bd_headset_attach`` would refuse, said with the models' names and before any device work (``ValueError``):
+    no member or more than 64; members on different embedders; more than 2048 outputs in all; for some depth, more than 2048
+    floats of hidden activations (the widths, each rounded up to 32, of the layers at that depth whose output is not the
+    member's own - hidden layers and a last layer in front of a softmax; members of one linear layer of at most 64 outputs run
+    on the fused kernel and take none).  Returns ``{name: slice}``, every member's columns of the logits."""
+    if not members:
+        raise ValueError("a set of heads needs at least one model (none given)")
+    if len(members) > HEADSET_MAX_MEMBERS:
+        raise ValueError(f"a set of heads takes at most {HEADSET_MAX_MEMBERS} models, not {len(members)}")
+    first_name, first = next(iter(members.items()))
+    for name, head in members.items():
+        if head.embeddername != first.embeddername:
+            raise ValueError(f"the models of a set share one embedder: {first_name!r} is on {first.embeddername!r}, "
+                             f"{name!r} on {head.embeddername!r}")
+    columns, at = {}, 0
+    for name, head in members.items():
+        n = int(head.layers[-1][0].shape[1])
+        if n != len(head.classes):
+            raise ValueError(f"model {name!r}: {len(head.classes)} classes, but its last layer gives {n} outputs")
+        columns[name] = slice(at, at + n)
+        at += n
+    if at > HEAD_MAX_WIDTH:
+        raise ValueError(f"the models' outputs sum to {at}, more than {HEAD_MAX_WIDTH}: "
+                         + ", ".join(f"{n} {c.stop - c.start}" for n, c in columns.items()))
+    stacks = {n: h for n, h in members.items() if not h.fused}
+    for d in range(max((len(h.layers) for h in stacks.values()), default=0)):
+        took = {n: (int(h.layers[d][0].shape[1]) + 31) // 32 * 32 for n, h in stacks.items()
+                if d < len(h.layers) and (d + 1 < len(h.layers) or h.layers[d][2] == "softmax")}
+        if sum(took.values()) > HEADSET_ROW:
+            raise ValueError(f"depth {d}: the hidden widths (each rounded up to 32) sum to {sum(took.values())}, more than "
+                             f"{HEADSET_ROW}: " + ", ".join(f"{n} {w}" for n, w in took.items()))
+    return columns
+
+
 def dense_chain(nodes, where: str = "saved_model.pb") -> List[Tuple[str, bool, str]]:
     """The Dense stack of a SavedModel graph, from its decoded nodes (``artifacts.saved_model_nodes``, or a recorded list
     of them): ``[(activation, has_bias, MatMul node name)]`` in order from the input.
