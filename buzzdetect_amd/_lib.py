@@ -197,6 +197,26 @@ HEADSET_PROTOTYPES = {
     "bd_headset_columns": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
+ENSEMBLE_ABI_VERSION = 1
+COMBINE_KINDS = {"none": 0, "mean": 1, "mean_probability": 2}
+LINKS = {None: 0, "softmax": 1, "sigmoid": 2}
+
+
+class bd_ensemble_output(C.Structure):
+    _fields_ = [("first_member", C.c_int32), ("n_members", C.c_int32), ("combine", C.c_int32), ("link", C.c_int32)]
+
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_ensemble.h
+ENSEMBLE_PROTOTYPES = {
+    "bd_ensemble_abi_version": (C.c_int, []),
+    "bd_ensemble_attach": (C.c_int, [C.c_void_p, C.POINTER(bd_ensemble_output), C.c_int32]),
+    "bd_ensemble_count": (C.c_int, [C.c_void_p]),
+    "bd_ensemble_outputs": (C.c_int, [C.c_void_p]),
+    "bd_ensemble_columns": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "bd_ensemble_combine_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(bd_ensemble_output), C.c_int32,
+                                           C.POINTER(C.c_int32), C.c_void_p, C.c_int32]),
+}
+
 ANYRATE_ABI_VERSION = 1
 
 # name -> (restype, argtypes); one entry per prototype in include/buzzdetect_anyrate.h
@@ -359,7 +379,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             raise RuntimeError(f"{path} is older than its sources and could not be rebuilt: {exc}") from exc
     lib = C.CDLL(path)
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
-            + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
+            + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ENSEMBLE_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
@@ -374,6 +394,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: head ABI version {lib.bd_head_abi_version()} != {HEAD_ABI_VERSION}; rebuild")
     if lib.bd_headset_abi_version() != HEADSET_ABI_VERSION:
         raise RuntimeError(f"{path}: head-set ABI version {lib.bd_headset_abi_version()} != {HEADSET_ABI_VERSION}; rebuild")
+    if lib.bd_ensemble_abi_version() != ENSEMBLE_ABI_VERSION:
+        raise RuntimeError(f"{path}: ensemble ABI version {lib.bd_ensemble_abi_version()} != {ENSEMBLE_ABI_VERSION}; rebuild")
     if lib.bd_anyrate_abi_version() != ANYRATE_ABI_VERSION:
         raise RuntimeError(f"{path}: any-ratio ABI version {lib.bd_anyrate_abi_version()} != {ANYRATE_ABI_VERSION}; rebuild")
     if lib.bd_train_abi_version() != TRAIN_ABI_VERSION:

@@ -268,6 +268,7 @@ constexpr int kHeadSetRegions = 3;
 struct HeadSet {
     int members = 0, outputs = 0;
     std::vector<int> first, count;           // per member: its columns of the logits
+    std::vector<int> last_act;               // per member: the activation of its last layer (BD_HEAD_*)
     char* dev = nullptr;                     // one allocation: packed kernels, biases, descriptors, tile tables
     struct Depth {
         const void* layers;                  // device, SetLayer[]: the layers of the stack-route members at this depth
@@ -290,5 +291,28 @@ void launch_dense_set(const HeadSet& set, int depth, const float* pooled, float*
                       hipStream_t stream);
 void launch_softmax_set(const HeadSet& set, const float* scratch, float* logits, int windows, hipStream_t stream);
 void launch_head_set(const HeadSet& set, const float* pooled, float* logits, int windows, hipStream_t stream);
+
+}  // namespace bd
+
+struct bd_ensemble_output;
+
+namespace bd {
+
+// ---- ensemble.hip ----
+// Outputs over the members of a set (include/buzzdetect_ensemble.h).  With one attached, the set's launches write the members'
+// columns into a fourth scratch region - region kEnsembleRegion, rows of HeadSet::outputs floats, packed like the logits they
+// replace - and launch_ensemble_combine writes the caller's logits from it.
+constexpr int kEnsembleRegion = kHeadSetRegions;
+struct Ensemble {
+    int n_outputs = 0, columns = 0;          // outputs (0: none attached), the sum of their widths
+    std::vector<int> first, count;           // per output: its columns of the logits
+    void* dev = nullptr;                     // device, one descriptor per output
+};
+// Checks `outputs` against the set, then uploads (synchronous).  BD_OK, or BD_EINVAL / BD_EHIP with *err set; *out is written on
+// success only.
+int ensemble_build(const HeadSet& set, const bd_ensemble_output* outputs, int n_outputs, Ensemble* out, std::string* err);
+void ensemble_free(Ensemble* ens);
+// wide = [windows][ld_wide] -> logits = [windows][ens.columns]
+void launch_ensemble_combine(const Ensemble& ens, const float* wide, int ld_wide, float* logits, int windows, hipStream_t stream);
 
 }  // namespace bd

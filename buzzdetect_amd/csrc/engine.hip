@@ -16,6 +16,7 @@
 #include "../../include/buzzdetect_anyrate.h"
 #include "../../include/buzzdetect_head.h"
 #include "../../include/buzzdetect_headset.h"
+#include "../../include/buzzdetect_ensemble.h"
 
 namespace {
 
@@ -86,6 +87,8 @@ struct bd_engine {
     float* d_stack = nullptr;         // one allocation for the stack's packed kernels and biases
     // or a set of heads (bd_headset_attach, headset.hip): n_classes is then the sum of the members' last widths
     bd::HeadSet set;
+    // and outputs over that set's members (bd_ensemble_attach, ensemble.hip): n_classes is then the sum of the outputs' widths
+    bd::Ensemble ens;
     // resampler: the filters of every (up, down) pair used so far, kept on the device until bd_destroy (nothing is
     // freed or re-uploaded on a rate change: hipFree would synchronise the device under the caller's streams)
     struct Taps {
@@ -631,6 +634,7 @@ int bd_destroy(bd_handle h) {
     if (h->d_amax) (void)hipFree(h->d_amax);
     if (h->d_stack) (void)hipFree(h->d_stack);
     bd::headset_free(&h->set);
+    bd::ensemble_free(&h->ens);
     delete h;
     return BD_OK;
 }
@@ -998,17 +1002,23 @@ int stack_head(Group& g, const float* pooled, float* scratch) {
     return BD_OK;
 }
 
-static_assert(BD_EMBEDDING_SIZE + bd::kHeadSetRegions * bd::kHeadSetRow <= kFloatsB, "pooled embeddings + the scratch of a set of heads fit either buffer");
+static_assert(BD_EMBEDDING_SIZE + (bd::kHeadSetRegions + 1) * bd::kHeadSetRow <= kFloatsB,
+              "pooled embeddings + the scratch of a set of heads + the members' columns under an ensemble fit either buffer");
+static_assert(bd::kEnsembleRegion == bd::kHeadSetRegions && BD_HEAD_MAX_WIDTH <= bd::kHeadSetRow, "the wide row of an ensemble is the region behind the set's own");
 
 // The attached set of heads (headset.hip) on pooled = [gw][1024]: one launch per depth of its deepest stack, one softmax row
 // pass, one launch for the members of the fused kind - whatever the number of members; scratch = kHeadSetRegions *
-// kHeadSetRow floats per window.  All in slot 28
+// kHeadSetRow floats per window.  With an ensemble over the set (ensemble.hip) the members' columns go to a fourth region, rows
+// of set.outputs floats packed as the logits would be, and one more launch writes the logits from it.  All in slot 28
 int set_head(Group& g, const float* pooled, float* scratch) {
     const bd::HeadSet& set = g.e->set;
+    const bd::Ensemble& ens = g.e->ens;
+    float* wide = ens.n_outputs ? scratch + bd::kEnsembleRegion * (size_t)g.gw * bd::kHeadSetRow : g.logits;
     for (size_t d = 0; d < set.depths.size(); ++d)
-        g.launch(28, [&] { bd::launch_dense_set(set, (int)d, pooled, scratch, g.logits, g.gw, g.stream); });
-    if (set.n_softmax) g.launch(28, [&] { bd::launch_softmax_set(set, scratch, g.logits, g.gw, g.stream); });
-    if (set.n_fused) g.launch(28, [&] { bd::launch_head_set(set, pooled, g.logits, g.gw, g.stream); });
+        g.launch(28, [&] { bd::launch_dense_set(set, (int)d, pooled, scratch, wide, g.gw, g.stream); });
+    if (set.n_softmax) g.launch(28, [&] { bd::launch_softmax_set(set, scratch, wide, g.gw, g.stream); });
+    if (set.n_fused) g.launch(28, [&] { bd::launch_head_set(set, pooled, wide, g.gw, g.stream); });
+    if (ens.n_outputs) g.launch(28, [&] { bd::launch_ensemble_combine(ens, wide, set.outputs, g.logits, g.gw, g.stream); });
     return BD_OK;
 }
 
@@ -1675,6 +1685,41 @@ int bd_headset_attach(bd_handle h, const bd_headset_member* members, int32_t n_m
     if (rc != BD_OK) return fail(rc, err);
     h->set = std::move(set);
     h->n_classes = h->set.outputs;
+    return BD_OK;
+}
+
+// ---- outputs over the set's members (header: buzzdetect_ensemble.h; kernel and host restatement: ensemble.hip) ----
+int bd_ensemble_count(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_ensemble_count: null handle");
+    return h->ens.n_outputs;
+}
+
+int bd_ensemble_outputs(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_ensemble_outputs: null handle");
+    return h->ens.columns;
+}
+
+int bd_ensemble_columns(bd_handle h, int32_t output, int32_t* first, int32_t* count) {
+    if (!h || !first || !count) return fail(BD_EINVAL, "bd_ensemble_columns: null argument");
+    if (output < 0 || output >= h->ens.n_outputs)
+        return fail(BD_EINVAL, "bd_ensemble_columns: output " + std::to_string(output) + " outside 0.." +
+                                   std::to_string(h->ens.n_outputs - 1));
+    *first = h->ens.first[output];
+    *count = h->ens.count[output];
+    return BD_OK;
+}
+
+int bd_ensemble_attach(bd_handle h, const bd_ensemble_output* outputs, int32_t n_outputs) {
+    if (!h || !outputs) return fail(BD_EINVAL, "bd_ensemble_attach: null argument");
+    if (!h->set.members) return fail(BD_EINVAL, "bd_ensemble_attach: the engine has no set of heads (bd_headset_attach comes first)");
+    if (h->ens.n_outputs) return fail(BD_EINVAL, "bd_ensemble_attach: the engine already has an ensemble");
+    BD_HIP(hipSetDevice(h->device));
+    std::string err;
+    bd::Ensemble ens;
+    const int rc = bd::ensemble_build(h->set, outputs, n_outputs, &ens, &err);
+    if (rc != BD_OK) return fail(rc, err);
+    h->ens = std::move(ens);
+    h->n_classes = h->ens.columns;
     return BD_OK;
 }
 

@@ -196,6 +196,7 @@ int headset_build(const bd_headset_member* members, int n_members, HeadSet* out,
         const int n_last = M.layers[M.n_layers - 1].n_out;
         set.first.push_back(col);
         set.count.push_back(n_last);
+        set.last_act.push_back(M.layers[M.n_layers - 1].activation);
         if (fused_route(M)) {
             const bd_head_layer& L = M.layers[0];
             for (int c = 0; c < L.n_out; ++c) {             // [1024][n] -> [class][1024], as bd_create keeps its head

@@ -240,7 +240,12 @@ class HipEngine:
         (``member_columns``, ``split``), each bit for bit what an engine with that model alone gives; ``members`` is the
         ordered ``{name: HeadWeights}``, ``classes`` the flat ``"<name>/<class>"`` list, ``head`` None.  An empty list, a name
         given twice, members on different embedders and a set beyond the library's limits raise ``ValueError`` before any
-        device work (``weights.check_head_set``)."""
+        device work (``weights.check_head_set``).
+        Ensembles (include/buzzdetect_ensemble.h): a model directory that is one (``weights.EnsembleWeights``) is an ordinary
+        model here - ``head`` is the ``EnsembleWeights``, ``classes`` its own, ``members`` None; its members run as a set and
+        one more launch per pass reduces them to the ensemble's columns on the device.  In a list or ``heads`` dict an ensemble
+        is one name among the others: one entry of ``member_columns`` / ``split``, its underlying members contiguous in the
+        set."""
         self._handle = C.c_void_p()
         self.members = None
         self.member_columns = None
@@ -251,6 +256,8 @@ class HipEngine:
         if heads is not None:
             heads = dict(heads)
             columns = weights.check_head_set(heads)        # host only: the library would refuse the same, later
+        if isinstance(head, weights.EnsembleWeights):
+            weights.check_head_set({"ensemble": head})
         self._lib = _lib.load()
         # the weights first (host only): a missing model fails the same way with or without a GPU in the box
         if embedder_blob is None:
@@ -283,6 +290,10 @@ class HipEngine:
             self.head = head
             self.classes = list(head.classes)
             self.n_classes = len(self.classes)
+        units = heads
+        if isinstance(head, weights.EnsembleWeights):
+            weights.check_head_set({modelname if isinstance(modelname, str) else "ensemble": head})    # (one loaded by name: here)
+            units = {"": head}
         if head is not None and head.fused:
             hk = np.ascontiguousarray(head.kernel, dtype=np.float32)
             hb = np.ascontiguousarray(head.bias, dtype=np.float32)
@@ -291,10 +302,10 @@ class HipEngine:
             w.n_classes = hb.size
         with torch.cuda.device(self.device):
             _lib.check(self._lib.bd_create(C.byref(self._handle), self.device_index, C.byref(w)))
-            if head is not None and not head.fused:
+            if units is not None:
+                self._attach_units(units)
+            elif head is not None and not head.fused:
                 self._attach_stack(head.layers)
-            if heads is not None:
-                self._attach_set(heads)
         # the handle is not thread-safe (include/buzzdetect_hip.h): every call that takes it goes through this lock, so a
         # writer thread that repeats a flagged chunk cannot interleave with the analyzer thread's next predict
         self._lock = threading.RLock()
@@ -323,9 +334,42 @@ class HipEngine:
         if self._lib.bd_head_outputs(self._handle) != self.n_classes:
             raise RuntimeError("bd_head_attach: the attached stack's width differs from the number of classes")
 
-    def _attach_set(self, heads: dict) -> None:
+    def _attach_units(self, units: dict) -> None:
+        """The heads of ``units`` = {name: HeadWeights or EnsembleWeights} as a set, and - where one of them is an ensemble -
+        ``bd_ensemble_attach`` with one output per name: an ensemble's members combined, a plain model passed through."""
+        if not any(isinstance(h, weights.EnsembleWeights) for h in units.values()):
+            return self._attach_set(units, dict(self.member_columns))
+        under = weights.expand_head_set(units)
+        wide, at = {}, 0
+        for name, h in under.items():
+            n = int(h.layers[-1][0].shape[1])
+            wide[name] = slice(at, at + n)
+            at += n
+        self._attach_set(under, wide)
+        out = (_lib.bd_ensemble_output * len(units))()
+        first = 0
+        for o, h in enumerate(units.values()):
+            ens = isinstance(h, weights.EnsembleWeights)
+            out[o].first_member = first
+            out[o].n_members = len(h.members) if ens else 1
+            out[o].combine = _lib.COMBINE_KINDS[h.combine] if ens else _lib.COMBINE_KINDS["none"]
+            out[o].link = _lib.LINKS[h.link] if ens else _lib.LINKS[None]
+            first += out[o].n_members
+        _lib.check(self._lib.bd_ensemble_attach(self._handle, out, len(units)))
+        if self._lib.bd_ensemble_outputs(self._handle) != self.n_classes:
+            raise RuntimeError("bd_ensemble_attach: the ensemble's width differs from the number of classes")
+        c_first, c_count = C.c_int32(), C.c_int32()
+        at = 0
+        for o, (name, h) in enumerate(units.items()):
+            _lib.check(self._lib.bd_ensemble_columns(self._handle, o, C.byref(c_first), C.byref(c_count)))
+            if (c_first.value, c_count.value) != (at, len(h.classes)):
+                raise RuntimeError(f"bd_ensemble_columns: output {name!r} sits at {c_first.value}..{c_first.value + c_count.value}, "
+                                   f"expected {at}..{at + len(h.classes)}")
+            at += len(h.classes)
+
+    def _attach_set(self, heads: dict, columns: dict) -> None:
         """``bd_headset_attach``: every member's layers (the library copies the arrays); the columns it reports are checked
-        against ``member_columns``."""
+        against ``columns``."""
         arr = (_lib.bd_headset_member * len(heads))()
         keep = []
         for m, head in enumerate(heads.values()):
@@ -342,10 +386,10 @@ class HipEngine:
             arr[m].layers = layers
             arr[m].n_layers = len(head.layers)
         _lib.check(self._lib.bd_headset_attach(self._handle, arr, len(heads)))
-        if self._lib.bd_headset_outputs(self._handle) != self.n_classes:
+        if self._lib.bd_headset_outputs(self._handle) != max(c.stop for c in columns.values()):
             raise RuntimeError("bd_headset_attach: the attached set's width differs from the number of classes")
         first, count = C.c_int32(), C.c_int32()
-        for m, (name, cols) in enumerate(self.member_columns.items()):
+        for m, (name, cols) in enumerate(columns.items()):
             _lib.check(self._lib.bd_headset_columns(self._handle, m, C.byref(first), C.byref(count)))
             if (first.value, first.value + count.value) != (cols.start, cols.stop):
                 raise RuntimeError(f"bd_headset_columns: member {name!r} sits at {first.value}..{first.value + count.value}, "

@@ -291,6 +291,23 @@ def write_model_dir(path: str, layers, classes: Optional[Sequence[str]] = None, 
     return path
 
 
+def write_ensemble_dir(path: str, members, classes: Sequence[str], combine: str = "mean", link: Optional[str] = None,
+                       embeddername: str = "yamnet_k2", digits_results: int = 2, metrics: Optional[str] = None) -> str:
+    """An ensemble's model directory (``weights.read_ensemble_dir``): ``members`` = {name: layers as ``write_model_dir`` takes
+    them}, each written as an ordinary model directory ``members/<name>/``; ``config_model.json`` carries the usual keys and
+    ``"ensemble": {"combine", "link", "members"}``; ``tests/metrics.csv`` is the ensemble's own.  No ``variables/`` at the top."""
+    os.makedirs(os.path.join(path, "tests"), exist_ok=True)
+    for name, layers in members.items():
+        write_model_dir(os.path.join(path, "members", name), layers, classes=classes, embeddername=embeddername,
+                        digits_results=digits_results, metrics=metrics)
+    with open(os.path.join(path, "config_model.json"), "w") as f:
+        json.dump({"classes": list(classes), "embeddername": embeddername, "digits_results": digits_results,
+                   "ensemble": {"combine": combine, "link": link, "members": list(members)}}, f)
+    with open(os.path.join(path, "tests", "metrics.csv"), "w") as f:
+        f.write(metrics if metrics is not None else default_metrics())
+    return path
+
+
 # the stacks the tests and tools/head_bench.py use: name -> (widths, activations)
 EXAMPLE_STACKS = {
     "relu_256_13": ([256, 13], ["relu", "linear"]),

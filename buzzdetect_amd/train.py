@@ -1156,7 +1156,11 @@ def cross_validate_head(embeddings, targets, classes, *, folds=None, groups=None
 
     The result's ``entries[g]`` hold ``oof_logits``, the K ``FitResult``, ``fold_best`` and ``metrics(class_name)``; ``best`` is
     the entry with the lowest mean ``fold_best``.  The final model stays the caller's own ``fit_head`` on all rows with
-    ``grid[best]``.  Hidden layers are outside the bank and not offered here: ``cross_validate_stack`` takes them."""
+    ``grid[best]``.  Hidden layers are outside the bank and not offered here: ``cross_validate_stack`` takes them.
+
+    The K folds are also the standard ensemble: ``save_ensemble(path, cv.entries[cv.best].fits,
+    metrics=cv.entries[cv.best].metrics(cls))`` writes them as one model.  The out-of-fold table scores every row with its single
+    held-out member, not with the mean of K, so it is a conservative estimate for the ensemble."""
     return _cross_validate(embeddings, targets, classes, (), (), folds, groups, fold_of_row, grid, loss, optimizer, epochs, batch_size,
                            seed, device, shared, fit_heads, lambda fits, **kw: TrainerBank([f.head.layers[0][:2] for f in fits], **kw))
 
@@ -1170,7 +1174,11 @@ def cross_validate_stack(embeddings, targets, classes, *, hidden=(), activations
     for bit, the ``fit_head(..., hidden=hidden, activations=activations)`` call ``fold_members`` describes; the out-of-fold
     logits come from one forward pass of a ``TrainerStackBank`` loaded with the fitted members.  The final model stays the
     caller's own ``fit_head`` on all rows with ``grid[best]`` and the same shape.  ``ValueError`` before any device work, a grid
-    entry's with ``grid[g]:`` in front."""
+    entry's with ``grid[g]:`` in front.
+
+    The K folds are also the standard ensemble: ``save_ensemble(path, cv.entries[cv.best].fits,
+    metrics=cv.entries[cv.best].metrics(cls))`` writes them as one model.  The out-of-fold table scores every row with its single
+    held-out member, not with the mean of K, so it is a conservative estimate for the ensemble."""
     def fit(*args, **kw):
         return fit_stacks(*args, hidden=hidden, activations=activations, **kw)
     return _cross_validate(embeddings, targets, classes, hidden, activations, folds, groups, fold_of_row, grid, loss, optimizer, epochs,
@@ -1257,4 +1265,76 @@ def save_model(path: str, fit, metrics: Optional[str] = None, embeddername: str 
     modeldir.write_model_dir(path, head.layers, classes=head.classes, embeddername=embeddername, digits_results=digits_results,
                              metrics=metrics if metrics is not None else METRICS_HEADER + "\n")
     modeldir.write_model_py(path, name, embeddername=embeddername, digits_results=digits_results)
+    return path
+
+
+def combine_logits(member_logits, combine: str = "mean", link: Optional[str] = None, dtype=np.float64) -> np.ndarray:
+    """What an ensemble gives for ``member_logits`` = ``[N, K, C]`` (row, member, class), in NumPy at ``dtype``: the statement of
+    include/buzzdetect_ensemble.h's formulas that the tests hold the device against, and a user's way to a ``metrics_table`` of
+    an ensemble on held-out rows.
+
+    "mean": ``(z[:, 0] + z[:, 1] + ...) * (1 / K)``, added in member order.  "mean_probability" with ``link`` "softmax":
+    ``log(mean_m softmax(z_m))``, with "sigmoid": ``logit(mean_m sigmoid(z_m))`` - both in the log domain (per-member
+    log-sum-exp over the classes, then a log-sum-exp over the members), finite for every finite input."""
+    dtype = np.dtype(dtype).type
+    z = np.asarray(member_logits, dtype=dtype)
+    if z.ndim != 3 or z.shape[1] < 1:
+        raise ValueError(f"combine_logits takes [rows, members, classes], not {tuple(z.shape)}")
+    k = z.shape[1]
+    one = dtype(1)
+
+    def lse(a, axis):
+        m = a.max(axis=axis, keepdims=True)
+        return (m + np.log(np.exp(a - m).sum(axis=axis, keepdims=True, dtype=dtype))).squeeze(axis)
+
+    def log_sigmoid(x):
+        return np.minimum(x, 0) - np.log1p(np.exp(-np.abs(x)))
+
+    if combine == "mean":
+        if link is not None:
+            raise ValueError(f'link {link!r} goes with combine "mean_probability" only')
+        total = z[:, 0].copy()
+        for m in range(1, k):
+            total += z[:, m]
+        return total * (one / dtype(k))
+    if combine != "mean_probability":
+        raise ValueError(f"unknown combine {combine!r}; an ensemble combines by mean or mean_probability")
+    with np.errstate(over="ignore", under="ignore"):
+        if link == "softmax":
+            a = np.maximum(z - lse(z, 2)[:, :, None], np.finfo(dtype).min)
+            return lse(a, 1) - np.log(dtype(k))
+        if link == "sigmoid":
+            return lse(log_sigmoid(z), 1) - lse(log_sigmoid(-z), 1)
+    raise ValueError(f'combine "mean_probability" needs link "softmax" or "sigmoid", not {link!r}')
+
+
+def save_ensemble(path: str, fits, *, combine: str = "mean", link: Optional[str] = None, names=None, metrics: Optional[str] = None,
+                  embeddername: str = "yamnet_k2", digits_results: int = 2) -> str:
+    """Write ``fits`` (``FitResult`` / ``weights.HeadWeights`` with identical classes - the K folds of a cross-validation entry,
+    the members of a sweep) as ONE model directory ``path`` = ``<models>/<modelname>`` that is an ensemble: every member an
+    ordinary model directory under ``members/<name>/`` (``names``, default ``member0`` ..), ``config_model.json`` with the
+    ``"ensemble"`` key.  ``HipEngine(modelname=...)``, ``analyze(modelname=...)`` and the drop-in model load it as they load any
+    model and get the members combined on the device (``combine`` / ``link``: ``weights.EnsembleWeights``).  ``metrics`` as
+    ``save_model`` takes it.  Everything is checked before anything is written (``ValueError``)."""
+    heads = [f.head if isinstance(f, FitResult) else f for f in fits]
+    if not heads:
+        raise ValueError("save_ensemble needs at least one fit")
+    names = [f"member{i}" for i in range(len(heads))] if names is None else [str(n) for n in names]
+    if len(names) != len(heads) or len(set(names)) != len(names):
+        raise ValueError(f"names must give every one of the {len(heads)} members a name of its own, not {names}")
+    for n in names:
+        if not n or os.path.basename(n) != n or n in (".", ".."):
+            raise ValueError(f"member name {n!r} must be a plain directory name")
+    ens = weights.EnsembleWeights(dict(zip(names, heads)), combine, link, list(heads[0].classes), embeddername, digits_results)
+    for n, h in ens.members.items():            # the members are written on this embedder, whatever the fits say
+        if isinstance(h, weights.EnsembleWeights):
+            raise weights.UnsupportedHeadError(f"save_ensemble: member {n!r} is an ensemble itself; ensembles do not nest")
+    same = weights.EnsembleWeights({n: weights.HeadWeights(h.layers, h.classes, embeddername) for n, h in ens.members.items()},
+                                   combine, link, ens.classes, embeddername, digits_results)
+    weights.check_ensemble(same, "save_ensemble")
+    weights.check_head_set({os.path.basename(os.path.normpath(path)): same})
+    text = metrics if metrics is not None else METRICS_HEADER + "\n"
+    modeldir.write_ensemble_dir(path, {n: h.layers for n, h in same.members.items()}, same.classes, combine, link, embeddername,
+                                digits_results, text)
+    modeldir.write_model_py(path, os.path.basename(os.path.normpath(path)), embeddername=embeddername, digits_results=digits_results)
     return path

@@ -276,6 +276,74 @@ class HeadWeights:
         return len(self.layers) == 1 and self.layers[0][2] == "linear" and self.layers[0][0].shape[1] <= HEAD_FUSED_MAX
 
 
+ENSEMBLE_COMBINES = ("mean", "mean_probability")
+ENSEMBLE_LINKS = ("softmax", "sigmoid")
+
+
+@dataclass
+class EnsembleWeights:
+    """An ensemble of heads over one embedder (include/buzzdetect_ensemble.h): the ordered ``members`` = {name: HeadWeights},
+    reduced on the device to ONE row of ``len(classes)`` logits per window.  ``combine`` = "mean" (the float32 mean of the
+    members' outputs, any common last activation; ``link`` None) or "mean_probability" (soft voting over members whose last
+    layer is linear, returned in the domain thresholds are taken in: ``link`` = "softmax" gives the log of the mean softmax,
+    "sigmoid" the logit of the mean sigmoid).  Everything else is what a ``HeadWeights`` carries, so ``analyze`` and the
+    drop-in model treat it as an ordinary model."""
+    members: "Dict[str, HeadWeights]"
+    combine: str
+    link: Optional[str]
+    classes: List[str]
+    embeddername: str = "yamnet_k2"
+    digits_results: int = 2
+    metrics_path: Optional[str] = None
+    source: str = ""
+
+    fused = False               # never the head fused behind the pool: its members run as a set
+
+
+def check_ensemble(ens: EnsembleWeights, where: str = "ensemble") -> None:
+    """What ``bd_ensemble_attach`` would refuse about one ensemble, and what the library cannot see (classes, embedders),
+    said with the members' names before any device work (``UnsupportedHeadError``; ``where`` names the file or model)."""
+    if ens.combine not in ENSEMBLE_COMBINES:
+        raise UnsupportedHeadError(f"{where}: unknown combine {ens.combine!r}; an ensemble combines by " + " or ".join(ENSEMBLE_COMBINES))
+    if ens.combine == "mean" and ens.link is not None:
+        raise UnsupportedHeadError(f'{where}: link {ens.link!r} goes with combine "mean_probability" only; "mean" takes null')
+    if ens.combine == "mean_probability" and ens.link not in ENSEMBLE_LINKS:
+        raise UnsupportedHeadError(f'{where}: combine "mean_probability" needs link "softmax" or "sigmoid", not {ens.link!r}')
+    if not 1 <= len(ens.members) <= HEADSET_MAX_MEMBERS:
+        raise UnsupportedHeadError(f"{where}: an ensemble has 1..{HEADSET_MAX_MEMBERS} members, not {len(ens.members)}")
+    first_name, first = next(iter(ens.members.items()))
+    for name, head in ens.members.items():
+        if isinstance(head, EnsembleWeights):
+            raise UnsupportedHeadError(f"{where}: member {name!r} is an ensemble itself; ensembles do not nest")
+        if list(head.classes) != list(ens.classes):
+            raise UnsupportedHeadError(f"{where}: member {name!r} has classes {list(head.classes)}, the ensemble {list(ens.classes)}")
+        if head.embeddername != ens.embeddername:
+            raise UnsupportedHeadError(f"{where}: member {name!r} is on embedder {head.embeddername!r}, the ensemble on "
+                                       f"{ens.embeddername!r}")
+        n = int(head.layers[-1][0].shape[1])
+        if n != len(ens.classes):
+            raise UnsupportedHeadError(f"{where}: member {name!r} gives {n} outputs for {len(ens.classes)} classes")
+        if head.layers[-1][2] != first.layers[-1][2]:
+            raise UnsupportedHeadError(f"{where}: member {name!r} ends in {head.layers[-1][2]!r}, member {first_name!r} in "
+                                       f"{first.layers[-1][2]!r}; the members of an ensemble share their last activation")
+        if ens.combine == "mean_probability" and head.layers[-1][2] != "linear":
+            raise UnsupportedHeadError(f'{where}: combine "mean_probability" takes members whose last layer is linear (it applies '
+                                       f"the {ens.link} itself); member {name!r} ends in {head.layers[-1][2]!r}")
+
+
+def expand_head_set(members: dict) -> "Dict[str, HeadWeights]":
+    """The heads the library runs for ``members`` = {name: HeadWeights or EnsembleWeights}, in its order: a plain model under
+    its own name, an ensemble's members - contiguous - as ``"<name>/<member>"``."""
+    out = {}
+    for name, head in members.items():
+        if isinstance(head, EnsembleWeights):
+            for m, h in head.members.items():
+                out[f"{name}/{m}"] = h
+        else:
+            out[name] = head
+    return out
+
+
 HEADSET_MAX_MEMBERS = 64    # members of a set of heads (BD_HEADSET_MAX_MEMBERS)
 HEADSET_ROW = 2048          # what the hidden activations of one depth of a set may take together, each width rounded up to 32
 
@@ -300,6 +368,8 @@ def check_head_set(members: "Dict[str, HeadWeights]") -> "Dict[str, slice]":
     on the fused kernel and take none).  Returns ``{name: slice}``, every member's columns of the logits."""
     if not members:
         raise ValueError("a set of heads needs at least one model (none given)")
+    if any(isinstance(h, EnsembleWeights) for h in members.values()):
+        return _check_units(members)
     if len(members) > HEADSET_MAX_MEMBERS:
         raise ValueError(f"a set of heads takes at most {HEADSET_MAX_MEMBERS} models, not {len(members)}")
     first_name, first = next(iter(members.items()))
@@ -324,6 +394,28 @@ def check_head_set(members: "Dict[str, HeadWeights]") -> "Dict[str, slice]":
         if sum(took.values()) > HEADSET_ROW:
             raise ValueError(f"depth {d}: the hidden widths (each rounded up to 32) sum to {sum(took.values())}, more than "
                              f"{HEADSET_ROW}: " + ", ".join(f"{n} {w}" for n, w in took.items()))
+    return columns
+
+
+def _check_units(units: dict) -> "Dict[str, slice]":
+    """``check_head_set`` where some values are ``EnsembleWeights``: every ensemble is checked on its own, the library's limits
+    (64 members, 2048 outputs, the per-depth rule) apply to the underlying members (``expand_head_set``, named
+    ``"<name>/<member>"``), and the columns returned are the PUBLIC ones - an ensemble takes ``len(classes)``, once."""
+    first_name, first = next(iter(units.items()))
+    for name, head in units.items():
+        if isinstance(head, EnsembleWeights):
+            check_ensemble(head, f"model {name!r}")
+        if head.embeddername != first.embeddername:
+            raise ValueError(f"the models of a set share one embedder: {first_name!r} is on {first.embeddername!r}, "
+                             f"{name!r} on {head.embeddername!r}")
+    check_head_set(expand_head_set(units))
+    columns, at = {}, 0
+    for name, head in units.items():
+        n = len(head.classes)
+        if not isinstance(head, EnsembleWeights) and n != int(head.layers[-1][0].shape[1]):
+            raise ValueError(f"model {name!r}: {n} classes, but its last layer gives {int(head.layers[-1][0].shape[1])} outputs")
+        columns[name] = slice(at, at + n)
+        at += n
     return columns
 
 
@@ -485,6 +577,48 @@ def read_model_dir(path: str, modelname: str = "") -> HeadWeights:
     return HeadWeights(layers, classes, cfg.get("embeddername", "yamnet_k2"), int(cfg.get("digits_results", 2)), metrics, path)
 
 
+def read_ensemble_dir(path: str, modelname: str = "") -> EnsembleWeights:
+    """An ensemble's model directory: ``config_model.json`` with the usual keys and ``"ensemble": {"combine", "link",
+    "members": [...]}``, every member an ordinary model directory ``members/<member>/`` (``read_model_dir``), the ensemble's
+    own ``tests/metrics.csv``.  No ``variables/`` of its own."""
+    cfg_path = os.path.join(path, "config_model.json")
+    with open(cfg_path) as f:
+        cfg = json.load(f)
+    spec = cfg.get("ensemble")
+    if not isinstance(spec, dict) or not isinstance(spec.get("members"), list) or "classes" not in cfg:
+        raise UnsupportedHeadError(f'{cfg_path}: "ensemble" must be {{"combine", "link", "members": [names]}} beside "classes"')
+    names = [str(n) for n in spec["members"]]
+    twice = sorted({n for n in names if names.count(n) > 1})
+    if twice:
+        raise UnsupportedHeadError(f"{cfg_path}: members named twice: {', '.join(twice)}")
+    if not 1 <= len(names) <= HEADSET_MAX_MEMBERS:
+        raise UnsupportedHeadError(f"{cfg_path}: an ensemble has 1..{HEADSET_MAX_MEMBERS} members, not {len(names)}")
+    members = {}
+    for name in names:
+        sub = os.path.join(path, "members", name)
+        sub_cfg = os.path.join(sub, "config_model.json")
+        if os.path.basename(name) != name or not os.path.isdir(sub) or not os.path.exists(sub_cfg):
+            raise UnsupportedHeadError(f"{cfg_path}: member {name!r} has no model directory {sub} (with config_model.json)")
+        with open(sub_cfg) as f:
+            if "ensemble" in json.load(f):
+                raise UnsupportedHeadError(f"{sub_cfg}: member {name!r} is an ensemble itself; ensembles do not nest")
+        members[name] = read_model_dir(sub, name)
+    metrics = os.path.join(path, "tests", "metrics.csv")
+    ens = EnsembleWeights(members, spec.get("combine"), spec.get("link"), list(cfg["classes"]), cfg.get("embeddername", "yamnet_k2"),
+                          int(cfg.get("digits_results", 2)), metrics if os.path.exists(metrics) else None, path)
+    check_ensemble(ens, cfg_path)
+    return ens
+
+
+def _is_ensemble_dir(path: str) -> bool:
+    try:
+        with open(os.path.join(path, "config_model.json")) as f:
+            cfg = json.load(f)
+    except (OSError, ValueError):
+        return False
+    return isinstance(cfg, dict) and "ensemble" in cfg
+
+
 def model_candidates(modelname: str, models_dir: Optional[str] = None) -> List[str]:
     """Directories ``load_head`` looks at, in order: ``models_dir/<modelname>`` alone when ``models_dir`` is given;
     else ``models/<modelname>`` under the working directory (the reference's ``cfg.DIR_MODELS``),
@@ -522,6 +656,9 @@ def load_head(modelname: str = PACKAGED_MODEL, models_dir: Optional[str] = None)
     Nothing found: ``FileNotFoundError`` naming every place looked at - never a silent fallback."""
     tried = []
     for c in model_candidates(modelname, models_dir):
+        if _is_ensemble_dir(c):          # an ensemble (read_ensemble_dir): its bundles sit under members/
+            _log.info(f"classifier ensemble: {c}")
+            return read_ensemble_dir(c, modelname)
         if os.path.exists(os.path.join(c, "variables", "variables.index")):
             _log.info(f"classifier head: {c}")
             return read_model_dir(c, modelname)
