@@ -61,6 +61,104 @@ __device__ __forceinline__ void split_f16(float x, float y, float z, float w, f1
 }
 __device__ __forceinline__ void split_f16(v4f a, f16x4& hi, f16x4& lo) { split_f16(a.x, a.y, a.z, a.w, hi, lo); }
 
+// Channel-major hand-off image (round 10): a stage tile a layer publishes from its ACCUMULATORS (lane = channel, registers =
+// positions) and the next product reads as its A operand (lane = position).  Two halves (hi, lo) of [32 k][96 positions] f16:
+// a k-row is 192 bytes = 24 chunks of 8 bytes (four consecutive tile rows), no padding, and chunk t of k-row c sits at chunk
+// t ^ ((c >> 1) & 7) of its row (the key touches the low three bits only: a chunk stays in its group of eight).  A lane writes
+// four of its own positions per ds_write_b64; the reader takes it back transposed with ds_read_b64_tr_b16 - lane 4 q + p of a
+// 16-lane group gives the address of k-row q of the block, positions 4 p .. 4 p + 3, and receives position (lane & 15) of the
+// four k-rows.  Why neither side meets a bank twice (checked below for every lane group):
+//   write  16 contiguous lanes = k-rows 16 a .. + 15 at one chunk t, bank (byte / 4) % 32.  A row is 48 dwords: odd rows start
+//          16 banks further, and the key gives the eight row pairs eight different chunks of the 16-dword group: 32 banks.
+//   read   a 32-lane half = 4 k-rows x 8 chunks (one group of eight), bank (byte / 4) % 64.  The four rows start at banks 0,
+//          48, 32, 16 and each covers the 16 dwords of its group: 64 banks.
+constexpr int kTrRowBytes = 192, kTrHalfBytes = 32 * kTrRowBytes, kTrSlotBytes = 2 * kTrHalfBytes;
+__host__ __device__ constexpr int tr_image_off(int half, int k, int chunk) {
+    return half * kTrHalfBytes + k * kTrRowBytes + ((chunk ^ ((k >> 1) & 7)) << 3);
+}
+// the reader's k-row and chunk: 16-lane group g = 2 h + gp (h: the k half of the MFMA lane, gp: rows 0-15 / 16-31 of the row
+// tile), lane 4 q + p of it, sub-read r (elements 0-3 / 4-7 of the fragment), k16 step s of the stage, row tile i
+__host__ __device__ constexpr int tr_read_k(int s, int h, int r, int q) { return 16 * s + 8 * h + 4 * r + q; }
+__host__ __device__ constexpr int tr_read_chunk(int i, int gp, int p) { return 8 * i + 4 * gp + p; }
+constexpr bool tr_image_is_bijection() {
+    bool seen[kTrSlotBytes / 8] = {};
+    for (int half = 0; half < 2; ++half)
+        for (int k = 0; k < 32; ++k)
+            for (int t = 0; t < 24; ++t) {
+                const int o = tr_image_off(half, k, t);
+                if (o < 0 || o >= kTrSlotBytes || o % 8 || seen[o / 8]) return false;
+                seen[o / 8] = true;
+            }
+    return true;
+}
+constexpr bool tr_image_writes_conflict_free() {       // ds_write_b64: 16 contiguous lanes, two dwords each, 32 banks
+    for (int half = 0; half < 2; ++half)
+        for (int a = 0; a < 2; ++a)
+            for (int t = 0; t < 24; ++t) {
+                unsigned banks = 0;
+                for (int l = 0; l < 16; ++l)
+                    for (int d = 0; d < 2; ++d) {
+                        const unsigned b = 1u << ((tr_image_off(half, 16 * a + l, t) / 4 + d) % 32);
+                        if (banks & b) return false;
+                        banks |= b;
+                    }
+            }
+    return true;
+}
+constexpr bool tr_image_reads_conflict_free() {        // ds_read_b64_tr_b16: 32-lane halves, two dwords each, 64 banks
+    for (int half = 0; half < 2; ++half)
+        for (int i = 0; i < 3; ++i)
+            for (int s = 0; s < 2; ++s)
+                for (int h = 0; h < 2; ++h)
+                    for (int r = 0; r < 2; ++r) {
+                        unsigned long long banks = 0;
+                        for (int gp = 0; gp < 2; ++gp)
+                            for (int q = 0; q < 4; ++q)
+                                for (int p = 0; p < 4; ++p)
+                                    for (int d = 0; d < 2; ++d) {
+                                        const unsigned long long b =
+                                            1ull << ((tr_image_off(half, tr_read_k(s, h, r, q), tr_read_chunk(i, gp, p)) / 4 + d) % 64);
+                                        if (banks & b) return false;
+                                        banks |= b;
+                                    }
+                    }
+    return true;
+}
+static_assert(tr_image_is_bijection(), "every (half, k, chunk) has its own 8 bytes of the slot, and they fill it");
+static_assert(tr_image_writes_conflict_free(), "a lane group of the publication meets no bank twice");
+static_assert(tr_image_reads_conflict_free(), "a lane half of the transposed read meets no bank twice");
+// Per-lane byte offset of sub-read r = 0 of (k16 step 0, row tile 0) in a half; sub-read 1 is tr_read_next() of it, k16 step 1
+// + 16 k-rows and row tile i + 64 i bytes (immediates).  k-row 8 h + 4 r + q has key (4 h + 2 r + (q >> 1)) & 7 whatever the
+// k16 step, so r = 1 is four rows further with bit 1 of the key = bit 4 of the byte offset flipped (rows are multiples of 64).
+__device__ __forceinline__ int tr_read_lane_off(int lane) {
+    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    return tr_image_off(0, tr_read_k(0, g >> 1, 0, q), tr_read_chunk(0, g & 1, p));
+}
+__host__ __device__ constexpr int tr_read_next(int off) { return (off ^ 16) + 4 * kTrRowBytes; }
+constexpr bool tr_read_next_holds() {
+    for (int lane = 0; lane < 64; ++lane) {
+        const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+        if (tr_read_next(tr_image_off(0, tr_read_k(0, g >> 1, 0, q), tr_read_chunk(0, g & 1, p))) !=
+            tr_image_off(0, tr_read_k(0, g >> 1, 1, q), tr_read_chunk(0, g & 1, p)))
+            return false;
+        for (int s = 0; s < 2; ++s)
+            for (int i = 0; i < 3; ++i)
+                for (int r = 0; r < 2; ++r)
+                    if (tr_image_off(0, tr_read_k(s, g >> 1, r, q), tr_read_chunk(i, g & 1, p)) !=
+                        tr_image_off(0, tr_read_k(0, g >> 1, r, q), tr_read_chunk(0, g & 1, p)) + 16 * s * kTrRowBytes + 64 * i)
+                        return false;
+    }
+    return true;
+}
+static_assert(tr_read_next_holds(), "the reader's immediates");
+// one A fragment (8 k of a lane's row) of the channel-major image: elements 0-3 from `p0`, 4-7 from `p1`.  EXEC must be all ones.
+__device__ __forceinline__ f16x8 tr_read_frag(const char* p0, const char* p1) {
+    typedef short s16x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) s16x4* lds4;
+    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4)p0), b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4)p1);
+    return __builtin_bit_cast(f16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
 // LDS operations the compiler must not reorder or wait for on its own: pw_res_kernel and l4_window_kernel count them (lgkmcnt).
 __device__ __forceinline__ unsigned pw_lds_addr(const void* p) {
     return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)p;

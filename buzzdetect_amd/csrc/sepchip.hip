@@ -34,10 +34,16 @@ namespace bd {
 
 namespace {
 
-// LDS image of one stage's A tile: two halves (hi, lo) of [96 rows][32 k] f16 = 64-byte rows, the 16-byte slot of a row
-// XORed with (row >> 2) & 3 (the swizzle of the round 2-5 kernels: the 8 rows a ds_read_b128 lane group touches land in different
-// banks), and rows 48.. pushed back by one row: the two half-waves of a publishing wave write rows r and r + 48 at once,
-// which would otherwise meet in the same 16 banks.
+// LDS images of one stage's A tile, both inside a slot of kChipSlotBytes (13 slots = 161 408 B):
+//   * the ROW image, pointwise 7's operand only (its LDS-DMA fills it): two halves (hi, lo) of [96 rows][32 k] f16 = 64-byte
+//     rows, the 16-byte slot of a row XORed with (row >> 2) & 3 (the 8 rows a ds_read_b128 lane group touches land in different
+//     banks), rows 48.. pushed back by one row;
+//   * the CHANNEL-MAJOR image (round 10, bd_device.h), every tile a layer publishes from its accumulators: two halves of
+//     [32 k][96 rows], 192-byte k-rows, 8-byte chunks XORed with (k >> 1) & 7, 12 288 B.  A lane (one channel, 48 consecutive
+//     tile rows) packs hi and lo along the rows as it splits them and writes 12 + 12 ds_write_b64 per column block where 96
+//     ds_write_b16 stood (1536 -> 384 wave-level writes per layer and tile); the K loop takes a fragment back with two
+//     ds_read_b64_tr_b16.  Both sides are free of bank conflicts (static_asserts in bd_device.h).  The barrier that frees the
+//     ring separates the two images.  Values, split, range guard, k order and MFMA operands are those of the row image.
 constexpr int kChipHalfBytes = 97 * 64;
 constexpr int kChipSlotBytes = 2 * kChipHalfBytes;
 
@@ -101,14 +107,19 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
     }
     CHIP_TS()
 
-    // publisher: lane (frow = k, fh) writes element k of rows 48 fh + r'.  Byte offset of k in a row whose swizzle key is m:
-    // (((k >> 3) ^ m) << 4) + 2 (k & 7) = wb0 ^ (m << 4) (bits 4-5 of everything else in wb0 are zero); rows follow as immediates
-    const int wb0 = fh * (48 * 64 + 64) + ((frow >> 3) << 4) + 2 * (frow & 7);
-    // reader: lane (frow, fh) supplies A[row 32 i + frow][k = 16 s + 8 fh ..] from slot (2 s + fh) ^ key, key = (row >> 2) & 3 =
+    // publisher (channel-major image, bd_device.h): lane (frow = k, fh) writes k-row frow, chunks 12 fh + j (tile rows 48 fh + 4 j
+    // .. + 3), 8 bytes per half and write; wk0 = the row's key in byte units
+    const int wk0 = ((frow >> 1) & 7) << 3;
+    // reader of pointwise 7's A operand (the ROW image its LDS-DMA fills: 64-byte rows [row][32 k], 16-byte slots XORed with
+    // (row >> 2) & 3, rows 48.. one row further): lane (frow, fh) supplies A[row 32 i + frow][k = 16 s + 8 fh ..] from slot
+    // (2 s + fh) ^ key, key = (row >> 2) & 3 =
     // (frow >> 2) & 3 for every i; s = 1 is the s = 0 address with bit 5 flipped.  Row tile 2 is row tile 0 + 4096 + 64 (an
     // immediate); row tile 1 straddles row 48 (the 64-byte skew starts at frow = 16) and keeps its own register.
     const int ra0 = frow * 64 + ((fh ^ ((frow >> 2) & 3)) << 4);
     const int ra1 = ra0 + 2048 + (frow >= 16 ? 64 : 0);
+    // reader of every other layer (channel-major image): the two transposed sub-reads of a fragment; k16 step and row tile are
+    // immediates (bd_device.h)
+    const int rt0 = tr_read_lane_off(lane), rt1 = tr_read_next(rt0);
     const unsigned lane16 = lane * 16, c4 = frow * 4;
 
     f32x16 acc[3][2];
@@ -116,7 +127,7 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
 
     // Depthwise 3 x 3 + shift + ReLU + split of column block J (stage ST) of the tile held as in2[y][x] = (window 2 fh,
     // window 2 fh + 1) at map position (y, x) of channel c: 48 outputs per lane, published into slot ST of the ring, or -
-    // always for J = 1, only waves 8 - NPEND .. 7 use them - kept as packed (hi | lo << 16) dwords in pend[].
+    // always for J = 1, only waves 8 - NPEND .. 7 use them - kept in pend[]: 24 dwords of hi pairs, then 24 of lo pairs.
 #define CHIP_DW(J, ST, TAPS)                                                                              \
     {                                                                                                     \
         float wt[9];                                                                                      \
@@ -124,52 +135,64 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
             wt[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(TAPS, c4, (t * K + 32 * (ST)) * 4, 0)); \
         const float shift = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(TAPS, c4, (9 * K + 32 * (ST)) * 4, 0)); \
         _Pragma("unroll") for (int y = 0; y < 6; ++y)                                                     \
-            _Pragma("unroll") for (int x = 0; x < 4; ++x) {                                               \
-                v2f a = {shift, shift};                                                                   \
-                _Pragma("unroll") for (int kh = 0; kh < 3; ++kh)                                          \
-                    _Pragma("unroll") for (int kw = 0; kw < 3; ++kw) {                                    \
-                        const int iy = y + kh - 1, ix = x + kw - 1;                                       \
-                        if (iy < 0 || iy >= 6 || ix < 0 || ix >= 4) continue;                             \
-                        a = __builtin_elementwise_fma(in2[iy][ix], v2f{wt[kh * 3 + kw], wt[kh * 3 + kw]}, a); \
-                    }                                                                                     \
+            _Pragma("unroll") for (int xp = 0; xp < 2; ++xp) {                                            \
+                v2f a[2];                                                                                 \
+                _Pragma("unroll") for (int d = 0; d < 2; ++d) {                                           \
+                    const int x = 2 * xp + d;                                                             \
+                    a[d] = v2f{shift, shift};                                                             \
+                    _Pragma("unroll") for (int kh = 0; kh < 3; ++kh)                                      \
+                        _Pragma("unroll") for (int kw = 0; kw < 3; ++kw) {                                \
+                            const int iy = y + kh - 1, ix = x + kw - 1;                                   \
+                            if (iy < 0 || iy >= 6 || ix < 0 || ix >= 4) continue;                         \
+                            a[d] = __builtin_elementwise_fma(in2[iy][ix], v2f{wt[kh * 3 + kw], wt[kh * 3 + kw]}, a[d]); \
+                        }                                                                                 \
+                }                                                                                         \
                 _Pragma("unroll") for (int w = 0; w < 2; ++w) {                                           \
-                    const float v = fmaxf(w ? a.y : a.x, 0.0f);                                           \
-                    unsigned pk = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)v);              \
-                    /* lo half = f16(v - hi) and the range guard's running maximum, in ONE ordered statement: as a plain */ \
+                    const float v0 = fmaxf(w ? a[0].y : a[0].x, 0.0f), v1 = fmaxf(w ? a[1].y : a[1].x, 0.0f); \
+                    const f16x2 h_ = {(_Float16)v0, (_Float16)v1};    /* hi of two neighbours along the tile's rows, packed */ \
+                    const unsigned hi_ = __builtin_bit_cast(unsigned, h_);                                \
+                    unsigned lo_;                                                                         \
+                    /* lo halves = f16(v - hi) and the range guard's running maximum, in ONE ordered statement: as a plain */ \
                     /* fmaxf chain the compiler sums the maxima up at the end and keeps (spills) all 48 values until then */ \
-                    asm volatile("v_fma_mixhi_f16 %0, %0, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\tv_max_f32 %1, %1, %2" \
-                                 : "+v"(pk), "+v"(rmax) : "v"(v));                                        \
-                    const int rl = 24 * w + 4 * y + x;      /* row 48 fh + rl */                          \
-                    if ((J) == 1) pend[rl] = pk;                                                          \
-                    else out0[rl] = pk;                                                                   \
+                    asm volatile("v_fma_mixlo_f16 %0, %2, -1.0, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"  \
+                                 "v_fma_mixhi_f16 %0, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"  \
+                                 "v_max_f32 %1, %1, %3\n\tv_max_f32 %1, %1, %4"                           \
+                                 : "=&v"(lo_), "+v"(rmax) : "v"(hi_), "v"(v0), "v"(v1));                  \
+                    const int ci = 2 * (6 * w + y) + xp;    /* rows 48 fh + 24 w + 4 y + 2 xp, + 1: dword xp of chunk 12 fh + 6 w + y */ \
+                    if ((J) == 1) { pend[ci] = hi_; pend[24 + ci] = lo_; }                                \
+                    else { out0[ci] = hi_; out0[24 + ci] = lo_; }                                         \
                 }                                                                                         \
             }                                                                                             \
     }
     // ... and their publication: column block 0 (stage wc) always, column block 1 (stage wc + 8) when its slot exists now
 #define CHIP_PUBLISH()                                                                                    \
     {                                                                                                     \
-        int wbl = wb0;       /* the four swizzle variants of the address are formed per use: as values of the whole kernel */ \
-        asm volatile("" : "+v"(wbl));                      /* they were spilled and reloaded behind vmcnt(0) waits */ \
-        char* const slot0 = sm + wc * kChipSlotBytes;                                                     \
-        _Pragma("unroll") for (int rl = 0; rl < 48; ++rl) CHIP_PUT(slot0, rl, out0[rl])                   \
+        int wkl = wk0;       /* the address variants are formed per use: as values of the whole kernel they were spilled */ \
+        asm volatile("" : "+v"(wkl));                      /* and reloaded behind vmcnt(0) waits */       \
+        char* const slot0 = sm + wc * kChipSlotBytes + frow * kTrRowBytes;                                \
+        _Pragma("unroll") for (int j = 0; j < 12; ++j) CHIP_PUT(slot0, j, out0)                           \
         if (wc + 8 < NSLOT) {                     /* one wave-uniform branch */                           \
-            char* const slot1 = sm + (wc + 8) * kChipSlotBytes;                                           \
-            _Pragma("unroll") for (int rl = 0; rl < 48; ++rl) CHIP_PUT(slot1, rl, pend[rl])               \
+            char* const slot1 = sm + (wc + 8) * kChipSlotBytes + frow * kTrRowBytes;                      \
+            _Pragma("unroll") for (int j = 0; j < 12; ++j) CHIP_PUT(slot1, j, pend)                       \
         }                                                                                                 \
     }
-#define CHIP_PUT(SLOT, RL, PK)                                                                            \
+    // chunk 12 fh + J of this lane's k-row: hi and lo, one ds_write_b64 each
+#define CHIP_PUT(ROW, J, PK)                                                                              \
     {                                                                                                     \
-        char* const p_ = (SLOT) + (wbl ^ ((((RL) >> 2) & 3) << 4)) + (RL) * 64;                           \
-        *reinterpret_cast<unsigned short*>(p_) = (unsigned short)(PK);                                    \
-        *reinterpret_cast<unsigned short*>(p_ + kChipHalfBytes) = (unsigned short)((PK) >> 16);           \
+        char* const p_ = (ROW) + ((96 * fh + 8 * (J)) ^ wkl);                                             \
+        *reinterpret_cast<u32x2*>(p_) = u32x2{PK[2 * (J)], PK[2 * (J) + 1]};                              \
+        *reinterpret_cast<u32x2*>(p_ + kTrHalfBytes) = u32x2{PK[24 + 2 * (J)], PK[25 + 2 * (J)]};         \
     }
     // taps [9][512] and shift [512] of a layer are one [10][512] table (engine.hip lays dw_b16 behind dw_w16; the launcher checks)
 #define CHIP_TAPS_RSRC(DW_W) __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DW_W), 0, 10 * K * 4, 0x00020000)
 
     // ---------------------------------------------------------------------- the K loop of one layer (KQ_C: k16 steps), the
     // weights WHI / WLO in B-fragment order; leaves the layer's product in acc
-    auto k_loop = [&](auto kq_c, const _Float16* const Wfhi, const _Float16* const Wflo) __attribute__((always_inline)) {
+    // row_c: the A operand lies in the ROW image (pointwise 7's, filled by LDS-DMA) and is read with ds_read_b128; otherwise in
+    // the channel-major image the layers publish, read transposed
+    auto k_loop = [&](auto kq_c, auto row_c, const _Float16* const Wfhi, const _Float16* const Wflo) __attribute__((always_inline)) {
         constexpr int KQL = decltype(kq_c)::value;
+        constexpr bool ROWIMG = decltype(row_c)::value;
         constexpr int NS = KQL / 2;               // stages
         constexpr int NP = NS > NSLOT ? NS - NSLOT : 0;    // of which pending
         static_assert(NP == 0 || NP == NPEND, "a layer of K = 512 or one that fits the ring");
@@ -202,7 +225,10 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         // bunches the four B loads of a k16 step at the top of the stage - an in-order wave then issues no MFMA while they
         // go out - and sinks the A reads to just before their use):
         //   A fragments   a ring of three (hi, lo) pairs, step t uses pair t mod 3 and requests the pair of step t + 2 (the one
-        //                 step t - 1 has finished with): two steps = 12 MFMAs between request and use, across stages too;
+        //                 step t - 1 has finished with): two steps = 12 MFMAs between request and use, across stages too.  In
+        //                 the channel-major image a fragment is TWO transposed reads (elements 0-3, 4-7), a pair four requests,
+        //                 lo before hi (the step's first MFMA takes lo): they fill the gaps the B loads leave, the last of a
+        //                 pair four to five MFMAs before its use at the closest (stage table below), 32 requests in 36 gaps;
         //   B fragments   two sets (k16 step 0 / 1 of a stage); a register is requested again in the gap after the last MFMA
         //                 that reads it, three steps = 18 MFMAs before its next use.
 #define CHIP_LAH(A, S, I) A = *reinterpret_cast<const f16x8*>(abase + (((I) == 1 ? ra1 : ra0) ^ ((S) << 5)) + ((I) == 2 ? 4096 + 64 : 0));
@@ -226,7 +252,7 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         M4 M5                                                                                             \
     }                                                                                                     \
     CHIP_MF(I, 1, AH, BH[1]) M6 CHIP_SB
-#define CHIP_STAGES(FROM, TO)                                                                             \
+#define CHIP_STAGES_ROW(FROM, TO)                                                                           \
     if ((FROM) < (TO)) {                                                                                  \
         f16x8 ah0, al0, ah1, al1, ah2, al2;                                                               \
         const char* abase = sm + ((FROM) < NSLOT ? (FROM) : (FROM) - NSLOT) * kChipSlotBytes;             \
@@ -245,17 +271,53 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
             CHIP_STEP(2, ah2, al2, bh1, bl1, CHIP_LAH(ah1, 0, 1), CHIP_LAL(al1, 0, 1), CHIP_NOP, CHIP_NOP, CHIP_NOP, CHIP_NOP) \
         }                                                                                                 \
     }
+        // the same in the channel-major image: ring entry n = (hNa, hNb | lNa, lNb), halves of a fragment
+#define CHIP_TR(V, HALF, S, I, R)                                                                         \
+    V = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4)(abase + ((R) ? rt1 : rt0) + 64 * (I) + 16 * kTrRowBytes * (S) + (HALF) * kTrHalfBytes));
+#define CHIP_FR(A, B) __builtin_bit_cast(f16x8, __builtin_shufflevector(A, B, 0, 1, 2, 3, 4, 5, 6, 7))
+#define CHIP_STAGES_TR(FROM, TO)                                                                          \
+    if ((FROM) < (TO)) {                                                                                  \
+        s16x4 h0a, h0b, l0a, l0b, h1a, h1b, l1a, l1b, h2a, h2b, l2a, l2b;                                 \
+        const char* abase = sm + ((FROM) < NSLOT ? (FROM) : (FROM) - NSLOT) * kChipSlotBytes;             \
+        CHIP_TR(l0a, 1, 0, 0, 0) CHIP_TR(l0b, 1, 0, 0, 1) CHIP_TR(h0a, 0, 0, 0, 0) CHIP_TR(h0b, 0, 0, 0, 1) \
+        CHIP_TR(l1a, 1, 0, 1, 0) CHIP_TR(l1b, 1, 0, 1, 1) CHIP_TR(h1a, 0, 0, 1, 0) CHIP_TR(h1b, 0, 0, 1, 1) \
+        _Pragma("nounroll") for (int kk = (FROM); kk < (TO); ++kk) {                                      \
+            const int q1 = 2 * kk + 1, q2 = 2 * kk + 2 < KQL ? 2 * kk + 2 : 0;    /* (the last stage re-reads step 0: unused) */ \
+            const char* const anext = sm + (kk + 1 < (TO) ? (kk + 1 < NSLOT ? kk + 1 : kk + 1 - NSLOT) : (kk < NSLOT ? kk : kk - NSLOT)) * kChipSlotBytes; \
+            CHIP_STEP(0, CHIP_FR(h0a, h0b), CHIP_FR(l0a, l0b), bh0, bl0, CHIP_LB(bhr, bh1, q1, 0), CHIP_LB(blr, bl1, q1, 0),     \
+                      CHIP_LB(bhr, bh1, q1, 1), CHIP_LB(blr, bl1, q1, 1), CHIP_TR(l2a, 1, 0, 2, 0), CHIP_TR(l2b, 1, 0, 2, 1))    \
+            CHIP_STEP(1, CHIP_FR(h1a, h1b), CHIP_FR(l1a, l1b), bh0, bl0, CHIP_TR(h2a, 0, 0, 2, 0), CHIP_TR(h2b, 0, 0, 2, 1),     \
+                      CHIP_TR(l0a, 1, 1, 0, 0), CHIP_TR(l0b, 1, 1, 0, 1), CHIP_TR(h0a, 0, 1, 0, 0), CHIP_TR(h0b, 0, 1, 0, 1))    \
+            CHIP_STEP(2, CHIP_FR(h2a, h2b), CHIP_FR(l2a, l2b), bh0, bl0, CHIP_TR(l1a, 1, 1, 1, 0), CHIP_TR(l1b, 1, 1, 1, 1),     \
+                      CHIP_LB(blr, bl0, q2, 0), CHIP_LB(bhr, bh0, q2, 0), CHIP_TR(h1a, 0, 1, 1, 0), CHIP_LB(blr, bl0, q2, 1))    \
+            CHIP_STEP(0, CHIP_FR(h0a, h0b), CHIP_FR(l0a, l0b), bh1, bl1, CHIP_LB(bhr, bh0, q2, 1), CHIP_TR(h1b, 0, 1, 1, 1),     \
+                      CHIP_TR(l2a, 1, 1, 2, 0), CHIP_TR(l2b, 1, 1, 2, 1), CHIP_TR(h2a, 0, 1, 2, 0), CHIP_TR(h2b, 0, 1, 2, 1))    \
+            abase = anext;         /* the first two steps of the next stage (the same stage again behind the last: unused) */ \
+            CHIP_STEP(1, CHIP_FR(h1a, h1b), CHIP_FR(l1a, l1b), bh1, bl1, CHIP_TR(l0a, 1, 0, 0, 0), CHIP_TR(l0b, 1, 0, 0, 1),     \
+                      CHIP_TR(h0a, 0, 0, 0, 0), CHIP_TR(h0b, 0, 0, 0, 1), CHIP_NOP, CHIP_NOP)                                   \
+            CHIP_STEP(2, CHIP_FR(h2a, h2b), CHIP_FR(l2a, l2b), bh1, bl1, CHIP_TR(l1a, 1, 0, 1, 0), CHIP_TR(l1b, 1, 0, 1, 1),     \
+                      CHIP_TR(h1a, 0, 0, 1, 0), CHIP_TR(h1b, 0, 0, 1, 1), CHIP_NOP, CHIP_NOP)                                   \
+        }                                                                                                 \
+    }
+#define CHIP_STAGES(FROM, TO)                                                                             \
+    if constexpr (ROWIMG) {                                                                               \
+        CHIP_STAGES_ROW(FROM, TO)                                                                         \
+    } else {                                                                                              \
+        CHIP_STAGES_TR(FROM, TO)                                                                          \
+    }
+        typedef short s16x4 __attribute__((ext_vector_type(4)));
+        typedef __attribute__((address_space(3))) s16x4* lds4;
         CHIP_STAGES(0, NP)
         CHIP_TS()
         if constexpr (NP > 0) {
             __syncthreads();                      // every wave has read stages 0 .. NPEND - 1: their slots are free
             CHIP_TS()
             if (wc >= 8 - NPEND) {
-                char* const slot = sm + (wc + 8 - NSLOT) * kChipSlotBytes;
-                int wbl = wb0;
-                asm volatile("" : "+v"(wbl));
+                char* const slot = sm + (wc + 8 - NSLOT) * kChipSlotBytes + frow * kTrRowBytes;
+                int wkl = wk0;
+                asm volatile("" : "+v"(wkl));
 #pragma unroll
-                for (int rl = 0; rl < 48; ++rl) CHIP_PUT(slot, rl, pend[rl])
+                for (int j = 0; j < 12; ++j) CHIP_PUT(slot, j, pend)
             }
         }
         CHIP_TS()
@@ -267,6 +329,10 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         CHIP_STAGES(NP, NS)
         CHIP_TS()
 #undef CHIP_STAGES
+#undef CHIP_STAGES_ROW
+#undef CHIP_STAGES_TR
+#undef CHIP_TR
+#undef CHIP_FR
 #undef CHIP_STEP
 #undef CHIP_BLOAD
 #undef CHIP_LB
@@ -361,7 +427,7 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         // in order - and the K loop's first step waits for B fragments requested in front of its barrier)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         CHIP_TS()
-        k_loop(std::integral_constant<int, 16>{}, ch.w7hi, ch.w7lo);
+        k_loop(std::integral_constant<int, 16>{}, std::true_type{}, ch.w7hi, ch.w7lo);
         next_layer(ch.dw_w[0], ch.u7, ch.b7);
     } else {
         // ------------------------------------------------------------------ layer 0: its depthwise reads the run's input
@@ -391,7 +457,7 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
 
     for (int li = 0; li < nl; ++li) {
         // ------------------------------------------------------------------ 1 x 1 convolution of layer li
-        k_loop(std::integral_constant<int, KQ>{}, chain_ptr<_Float16>(2, li), chain_ptr<_Float16>(3, li));
+        k_loop(std::integral_constant<int, KQ>{}, std::false_type{}, chain_ptr<_Float16>(2, li), chain_ptr<_Float16>(3, li));
         if (li + 1 == nl) break;
         // ------------------------------------------------------------------ depthwise of layer li + 1 on the accumulators
         next_layer(chain_ptr<float>(0, li + 1), chain_ptr<float>(4, li), chain_ptr<float>(5, li));

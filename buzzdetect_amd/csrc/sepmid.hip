@@ -6,9 +6,9 @@
 // A tile is ONE window (96 positions of the 12 x 8 map).  The scheme is sepchip.hip's:
 //   * 8 MFMA waves (two per SIMD, 256 VGPRs), wave w owns output column tile w (layers 5, 6: 256 columns = 8 tiles; layer 7: 512
 //     columns, tiles w and w + 8);
-//   * an A operand is published into LDS one 32-channel STAGE at a time (split-f16 hi | lo, sepchip.hip's image: 64-byte rows,
-//     16-byte slots XORed with (row >> 2) & 3, rows 48.. skewed by 64 bytes) - stage s of a layer is column tile s of the layer
-//     before, i.e. wave s's own output;
+//   * an A operand is published into LDS one 32-channel STAGE at a time (split-f16 hi | lo; A5 and A7 in the row image: 64-byte
+//     rows, 16-byte slots XORed with (row >> 2) & 3, rows 48.. skewed by 64 bytes; A6 channel-major, round 10 below) - stage s
+//     of a layer is column tile s of the layer before, i.e. wave s's own output;
 //   * the tile's row order in LDS is NOT the map's: position (y, x) sits at row 48 (x >> 2) + 4 y + (x & 3).  With that order a
 //     lane (channel c, half h) of the 32 x 32 accumulator layout holds, after one v_permlane32_swap per register pair, the
 //     columns 4 h .. 4 h + 3 of ALL twelve map rows of its channel; the one column it lacks for a 3 x 3 window (x = 4 h - 1 or
@@ -26,6 +26,11 @@
 // Round 9: a wave reads its share of the window (the f32 depthwise-5 output) as one contiguous 6 KB run, six 16-byte loads per
 // lane where 24 dword loads stood, and a lane - now four channels of one position - splits them and writes hi and lo as one
 // 8-byte LDS write each (12 per lane and window, 48 two-byte writes before).  The LDS image and every bit are unchanged.
+// Round 10: A6 - published from the accumulators behind depthwise 6, one channel per lane - takes the channel-major image of
+// bd_device.h ([32 k][96 positions] per half, 8-byte chunks XORed with (k >> 1) & 7): a lane's 48 outputs are 48 consecutive
+// tile rows, so hi and lo are packed along the rows as they are split and leave as 12 + 12 ds_write_b64 where 96 ds_write_b16
+// stood, and pointwise 6 reads its A fragments back with two ds_read_b64_tr_b16 each.  A5 (four channels of one position per
+// lane) and A7 keep the row image and ds_read_b128.  Values, split, range guard, k order and MFMA operands are unchanged.
 #include "bd_device.h"
 
 #include <type_traits>
@@ -75,8 +80,6 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
             dbg[(wc == 5 ? 64 : 0) + tsn] = __builtin_amdgcn_s_memtime();                                 \
         ++tsn;                                                                                            \
     }
-    // publisher (96-row stages): lane (k = frow, fh) writes rows 48 fh + rl; byte offset of k in a row whose key is m = wb0 ^ (m << 4)
-    const int wb0 = fh * (48 * 64 + 64) + ((frow >> 3) << 4) + 2 * (frow & 7);
     // publisher of A5 (lane = channels 4 frow .. + 3 of a position whose x & 1 is fh): stage frow >> 3, slot (frow & 7) >> 1 (bits
     // 4-5, clear in everything else here: the key is XORed in per row), 8 bytes per half slot, + fh rows
     const int wb5 = (frow >> 3) * kSlotA + fh * 64 + (((frow & 7) >> 1) << 4) + 8 * (frow & 1);
@@ -86,19 +89,29 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
     // reader: lane (frow, fh) supplies A[row 32 i + frow][k = 16 s + 8 fh ..]: slot (2 s + fh) ^ key, key = (frow >> 2) & 3
     const int ra0 = frow * 64 + ((fh ^ ((frow >> 2) & 3)) << 4);
     const int ra1 = ra0 + 2048 + (frow >= 16 ? 64 : 0);
+    // A6 (channel-major image, bd_device.h): the publisher's key in byte units, and the transposed reader's two sub-reads
+    const int wt6 = ((frow >> 1) & 7) << 3;
+    const int rt0 = tr_read_lane_off(lane), rt1 = tr_read_next(rt0);
+    static_assert(kTrSlotBytes <= kSlotA, "A6's image fits the slots A5 leaves");
     const unsigned lane16 = lane * 16, c4 = frow * 4;
 
-#define MID_PUT(BASE, RL, PK)                                                                             \
-    {                                                                                                     \
-        char* const p_ = (BASE) + (wbl ^ ((((RL) >> 2) & 3) << 4)) + (RL) * 64;                           \
-        *reinterpret_cast<unsigned short*>(p_) = (unsigned short)(PK);                                    \
-        *reinterpret_cast<unsigned short*>(p_ + kHalfA) = (unsigned short)((PK) >> 16);                   \
-    }
     // v -> (hi | lo << 16), the range guard's running maximum in the same ordered statement (sepchip.hip)
 #define MID_SPLIT(V, PK)                                                                                  \
     unsigned PK = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)(V));                            \
     asm volatile("v_fma_mixhi_f16 %0, %0, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\tv_max_f32 %1, %1, |%2|"   \
                  : "+v"(PK), "+v"(rmax) : "v"(V));
+    // two values, neighbours along the tile's rows -> HI = (hi0 | hi1 << 16), LO likewise: the same conversions, packed
+#define MID_SPLIT2(V0, V1, HI, LO)                                                                        \
+    {                                                                                                     \
+        const f16x2 h_ = {(_Float16)(V0), (_Float16)(V1)};                                                \
+        unsigned hi_ = __builtin_bit_cast(unsigned, h_), lo_;                                             \
+        asm volatile("v_fma_mixlo_f16 %0, %2, -1.0, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"              \
+                     "v_fma_mixhi_f16 %0, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"              \
+                     "v_max_f32 %1, %1, |%3|\n\tv_max_f32 %1, %1, |%4|"                                   \
+                     : "=&v"(lo_), "+v"(rmax) : "v"(hi_), "v"(V0), "v"(V1));                              \
+        HI = hi_;                                                                                         \
+        LO = lo_;                                                                                         \
+    }
     // one k16 step of a K loop: NI row tiles x NJ column tiles, A from LDS at ABASE (row tile i: ra0 / ra1 / ra0 + 4160), B in BH / BL
 #define MID_MMA(ACC, AH, AL, BHV, BLV)                                                                    \
     if constexpr (!PLAIN) {                                                                               \
@@ -212,7 +225,7 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
         // ---- depthwise 6 in registers; its outputs wait (packed) for the ring: A6 takes the slots A5 is still read from
         const __amdgpu_buffer_rsrc_t r6h = MID_RSRC(a.w6h, 256 * 256 * 2), r6l = MID_RSRC(a.w6l, 256 * 256 * 2);
         {
-            unsigned out6[48];
+            u32x2 out6h[12], out6l[12];           // chunk j = tile rows 48 fh + 4 j .. + 3 of channel frow: hi and lo, packed along rows
             {
                 const __amdgpu_buffer_rsrc_t ur = MID_RSRC(a.u5, 1024), br = MID_RSRC(a.b5, 1024), tr = MID_RSRC(a.dw6, 10 * 256 * 4);
                 const float u = MID_LD32(ur, c4, 128 * wc), b = MID_LD32(br, c4, 128 * wc);
@@ -230,18 +243,22 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
 #pragma unroll
                 for (int y = 0; y < 6; ++y)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v2f sacc = {shift, shift};
+                    for (int ep = 0; ep < 2; ++ep) {
+                        v2f sacc[2];
 #pragma unroll
-                        for (int kh = 0; kh < 3; ++kh)
+                        for (int d = 0; d < 2; ++d) {
+                            const int e = 2 * ep + d;
+                            sacc[d] = v2f{shift, shift};
 #pragma unroll
-                            for (int kw = 0; kw < 3; ++kw)
-                                sacc = __builtin_elementwise_fma(in2[y + kh][e + kw], v2f{wt[kh * 3 + kw], wt[kh * 3 + kw]}, sacc);
+                            for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+                                for (int kw = 0; kw < 3; ++kw)
+                                    sacc[d] = __builtin_elementwise_fma(in2[y + kh][e + kw], v2f{wt[kh * 3 + kw], wt[kh * 3 + kw]}, sacc[d]);
+                        }
 #pragma unroll
                         for (int w = 0; w < 2; ++w) {
-                            const float o = fmaxf(w ? sacc.y : sacc.x, 0.0f);
-                            MID_SPLIT(o, pk)
-                            out6[4 * (y + 6 * w) + e] = pk;
+                            const float o0 = fmaxf(w ? sacc[0].y : sacc[0].x, 0.0f), o1 = fmaxf(w ? sacc[1].y : sacc[1].x, 0.0f);
+                            MID_SPLIT2(o0, o1, out6h[y + 6 * w][ep], out6l[y + 6 * w][ep])
                         }
                     }
             }
@@ -252,11 +269,16 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
                 bh[q] = MID_LD128(r6h, lane16, (wc * 16 + q) * 1024);
                 bl[q] = MID_LD128(r6l, lane16, (wc * 16 + q) * 1024);
             }
-            int wbl = wb0;
-            asm volatile("" : "+v"(wbl));
-            char* const slot = sm + wc * kSlotA;
+            // A6 in the channel-major image (bd_device.h): k-row frow of stage wc, chunks 12 fh + j, 8 bytes per write
+            int wkey = wt6;
+            asm volatile("" : "+v"(wkey));
+            char* const slot = sm + wc * kSlotA + frow * kTrRowBytes;
 #pragma unroll
-            for (int rl = 0; rl < 48; ++rl) MID_PUT(slot, rl, out6[rl])
+            for (int j = 0; j < 12; ++j) {
+                char* const p_ = slot + ((96 * fh + 8 * j) ^ wkey);
+                *reinterpret_cast<u32x2*>(p_) = out6h[j];
+                *reinterpret_cast<u32x2*>(p_ + kTrHalfBytes) = out6l[j];
+            }
         }
         __syncthreads();                          // A6 published
         MID_TS()
@@ -274,11 +296,11 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
                     bh[(q + 2) % 3] = MID_LD128(r6h, lane16, (wc * KQ + q + 2) * 1024);
                     bl[(q + 2) % 3] = MID_LD128(r6l, lane16, (wc * KQ + q + 2) * 1024);
                 }
-                const char* const ab = sm + (q >> 1) * kSlotA;
+                const char* const ab = sm + (q >> 1) * kSlotA + (q & 1) * 16 * kTrRowBytes;
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
-                    const char* const ap = ab + ((i == 1 ? ra1 : ra0) ^ ((q & 1) << 5)) + (i == 2 ? 4096 + 64 : 0);
-                    const f16x8 ah = *reinterpret_cast<const f16x8*>(ap), al = *reinterpret_cast<const f16x8*>(ap + kHalfA);
+                    const f16x8 ah = tr_read_frag(ab + rt0 + 64 * i, ab + rt1 + 64 * i);
+                    const f16x8 al = tr_read_frag(ab + rt0 + 64 * i + kTrHalfBytes, ab + rt1 + 64 * i + kTrHalfBytes);
                     MID_MMA(acc[i], ah, al, bh[q % 3], bl[q % 3])
                 }
             }
@@ -431,8 +453,8 @@ __global__ __launch_bounds__(512, 2) void sep_mid_kernel(const MidArgs a, const 
     }
     range_report(rmax, range_flag);
 #undef MID_TS
-#undef MID_PUT
 #undef MID_SPLIT
+#undef MID_SPLIT2
 #undef MID_MMA
 #undef MID_TILE_TO_MAP
 #undef MID_HALO
