@@ -28,7 +28,7 @@ FILE_FLAGS = {
     "sepchipf32.hip": ("-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"),
     "sepmidf32.hip": ("-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"),
 }
-HEADERS = ("bd_internal.h", "bd_device.h", "headtrain_device.h", "dense_device.h", "ensemble_device.h", os.path.join("..", "..", "include", "buzzdetect_hip.h"),
+HEADERS = ("bd_internal.h", "bd_device.h", "headtrain_device.h", "headtrain_host.h", "dense_device.h", "ensemble_device.h", os.path.join("..", "..", "include", "buzzdetect_hip.h"),
            os.path.join("..", "..", "include", "buzzdetect_flac.h"), os.path.join("..", "..", "include", "buzzdetect_pcm.h"),
            os.path.join("..", "..", "include", "buzzdetect_head.h"),
            os.path.join("..", "..", "include", "buzzdetect_headset.h"),

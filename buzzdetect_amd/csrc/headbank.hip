@@ -16,34 +16,23 @@
 // bank_apply_kernel adds an element's partials in ascending slice order and applies its member's decay and update; a frozen
 // member's workgroups return at once.  A member's rate, bias-corrected rate, decay and frozen flag travel by value in the
 // launch (Members), kMembersPerLaunch at a time: nothing a later bd_bank_set_* could overwrite before the step has run.
+//
+// This file: the bank's kernels, Shape and the group layout of its pool, and the launches of its entry points.  The checks,
+// Members and the members' state on the host (MemberState: the validated setters, the step counts, the launch arguments with
+// the bias-corrected Adam rate), the running losses and the workspace's test hooks are headtrain_host.h's, shared with
+// headtrain.hip and stackbank.hip.
 #include "headtrain_device.h"
-
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
+#include "headtrain_host.h"
 
 #include "../../include/buzzdetect_bank.h"
 
 namespace bd {
-
-void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
-
 namespace {
-
-using namespace train;
 
 constexpr int kGroupCols = BD_BANK_GROUP_COLUMNS;
 constexpr int kIn = BD_EMBEDDING_SIZE;
 constexpr int64_t kGroupFloats = (int64_t)(kIn + 1) * kGroupCols;      // stride of a group's [1025][ng] block
-constexpr int kMembersPerLaunch = 64;
 static_assert(kGroupCols == BD_TRAIN_FUSED_MAX_WIDTH && kGroupCols % 32 == 0, "a group is the fused kernel's two column tiles");
-
-struct Members {                    // the members first .. first + count of a launch, by value
-    int first, count;
-    float lr[kMembersPerLaunch], lr_t[kMembersPerLaunch], decay[kMembersPerLaunch];
-    int frozen[kMembersPerLaunch];
-};
 
 struct Shape {
     int M, C, mpg, groups;          // mpg: members per group
@@ -146,80 +135,43 @@ __global__ __launch_bounds__(256) void bank_copy_member_kernel(float* __restrict
     dst[at] = src[at];
 }
 
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
-#define BDB_HIP(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(BD_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 }  // namespace
 }  // namespace bd
 
-struct bd_bank_s {
-    int device = 0, loss = 0;
+struct bd_bank_s : bd::TrainHandle {
     bd::Shape s{};
-    bd_train_optimizer opt{};       // kind, betas, epsilon; learning_rate: the members' first
-    std::vector<float> lr, wd;
-    std::vector<int> frozen, has_snapshot;
-    std::vector<int64_t> step;
-    float* pool = nullptr;          // one allocation behind every pointer below
     float *p = nullptr, *grad = nullptr, *m = nullptr, *v = nullptr, *snap = nullptr;      // [groups][kGroupFloats]
     float *z = nullptr, *g = nullptr;                                                      // [groups][max_batch][64]
-    float* ws = nullptr;            // [slices of max_batch][groups][kGroupFloats]
-    int64_t ws_floats = 0;
     float* row_loss = nullptr;      // [M][max_batch]
-    double* acc = nullptr;          // [M][2]: running loss sum, rows
-    hipStream_t last = nullptr;
+    // ws: [slices of max_batch][groups][kGroupFloats]
 };
 
 namespace bd {
 namespace {
 
-int check_member(const bd_bank_s* b, int32_t member, const char* who) {
-    if (!b) return fail(BD_EINVAL, std::string(who) + ": null handle");
-    if (member < 0 || member >= b->s.M) return fail(BD_EINVAL, std::string(who) + ": no such member");
+// where member's columns begin in its group's block, and how many columns that block has (the host's group_width)
+struct Columns {
+    int64_t block;                  // the group's block in p, grad, m, v, snap
+    int ng, col0;
+};
+
+Columns columns_of(const Shape& s, int member) {
+    const int group = member / s.mpg;
+    return {group * kGroupFloats, (s.mpg < s.M - group * s.mpg ? s.mpg : s.M - group * s.mpg) * s.C, (member % s.mpg) * s.C};
+}
+
+// member's columns of the parameters -> its columns of the snapshot (to_snapshot) or back, on the caller's stream
+int copy_member(bd_bank_s* b, int32_t member, bool to_snapshot, void* stream_) {
+    hipStream_t stream;
+    const int rc = enter(b, stream_, &stream);
+    if (rc < 0) return rc;
+    const Columns c = columns_of(b->s, member);
+    float *p = b->p + c.block, *snap = b->snap + c.block;
+    hipLaunchKernelGGL(bank_copy_member_kernel, dim3(((kIn + 1) * b->s.C + 255) / 256), dim3(256), 0, stream, to_snapshot ? snap : p,
+                       to_snapshot ? p : snap, b->s.C, c.ng, c.col0);
+    BD_TRAIN_HIP(hipGetLastError());
     return BD_OK;
 }
-
-int check_batch(const bd_bank_s* b, const float* X, int64_t ldx, int32_t B, const char* who) {
-    if (B < 1 || B > b->s.max_batch) return fail(BD_EINVAL, std::string(who) + ": B must be in 1..max_batch");
-    if (ldx < BD_EMBEDDING_SIZE || ldx % 4 || (reinterpret_cast<uintptr_t>(X) & 15u))
-        return fail(BD_EINVAL, std::string(who) + ": X needs 16-byte alignment and ldx >= 1024, a multiple of 4");
-    return BD_OK;
-}
-
-int check_weights(const float* row_w, int64_t ldw, int32_t B, const char* who) {
-    if (!row_w) return BD_OK;
-    if (reinterpret_cast<uintptr_t>(row_w) & 3u) return fail(BD_EINVAL, std::string(who) + ": row_weights is not aligned to a float");
-    if (ldw < B) return fail(BD_EINVAL, std::string(who) + ": ldw must be at least B");
-    return BD_OK;
-}
-
-// the launch arguments of members first .. first + count as the host has them now (step counts already advanced)
-Members members_of(const bd_bank_s* b, int first, int count) {
-    Members a{};
-    a.first = first;
-    a.count = count;
-    for (int j = 0; j < count; ++j) {
-        const int mb = first + j;
-        const float lr = b->lr[mb];
-        a.lr[j] = lr;
-        a.decay[j] = b->wd[mb] != 0.0f ? lr * b->wd[mb] : 0.0f;
-        a.frozen[j] = b->frozen[mb];
-        if (b->opt.kind == BD_TRAIN_ADAM && b->step[mb] > 0)
-            a.lr_t[j] = (float)((double)lr * std::sqrt(1.0 - std::pow((double)b->opt.beta_2, (double)b->step[mb])) /
-                                (1.0 - std::pow((double)b->opt.beta_1, (double)b->step[mb])));
-    }
-    return a;
-}
-
-float inv_of(const bd_bank_s* b, int B) { return 1.0f / (b->loss == BD_TRAIN_BINARY ? (float)B * (float)b->s.C : (float)B); }
-double scale_of(const bd_bank_s* b, int B) { return 1.0 / (b->loss == BD_TRAIN_BINARY ? (double)B * b->s.C : (double)B); }
 
 }  // namespace
 }  // namespace bd
@@ -232,21 +184,16 @@ int bd_bank_abi_version(void) { return BD_BANK_ABI_VERSION; }
 
 int bd_bank_create(int device, const bd_head_layer* layers, int32_t n_members, int32_t loss, const bd_train_optimizer* opt,
                    int32_t max_batch, bd_bank* out) {
-    if (!out || !layers || !opt) return fail(BD_EINVAL, "bd_bank_create: null argument");
+    const std::string who = "bd_bank_create";
+    if (!out || !layers || !opt) return fail(BD_EINVAL, who + ": null argument");
     *out = nullptr;
-    if (n_members < 1 || n_members > BD_BANK_MAX_MEMBERS) return fail(BD_EINVAL, "bd_bank_create: the members must number 1..4096");
-    if (loss != BD_TRAIN_CATEGORICAL && loss != BD_TRAIN_BINARY) return fail(BD_EINVAL, "bd_bank_create: unknown loss");
-    if (opt->kind != BD_TRAIN_SGD && opt->kind != BD_TRAIN_ADAM) return fail(BD_EINVAL, "bd_bank_create: unknown optimizer");
-    if (!(opt->learning_rate > 0.0f) || !std::isfinite(opt->learning_rate))
-        return fail(BD_EINVAL, "bd_bank_create: learning_rate must be positive and finite");
-    if (opt->kind == BD_TRAIN_ADAM && !(opt->beta_1 >= 0.0f && opt->beta_1 < 1.0f && opt->beta_2 >= 0.0f && opt->beta_2 < 1.0f &&
-                                        opt->epsilon > 0.0f))
-        return fail(BD_EINVAL, "bd_bank_create: Adam needs 0 <= beta < 1 and epsilon > 0");
-    if (max_batch < 1 || max_batch > BD_TRAIN_MAX_BATCH) return fail(BD_EINVAL, "bd_bank_create: max_batch must be in 1..65536");
+    if (n_members < 1 || n_members > BD_BANK_MAX_MEMBERS) return fail(BD_EINVAL, who + ": the members must number 1..4096");
+    int rc = bd::check_training_setup(who, loss, opt, max_batch);
+    if (rc < 0) return rc;
     const int C = layers[0].n_out;
-    if (C < 1 || C > BD_TRAIN_FUSED_MAX_WIDTH) return fail(BD_EINVAL, "bd_bank_create: n_out must be in 1..64 (a bank holds one-layer heads of the fused width)");
+    if (C < 1 || C > BD_TRAIN_FUSED_MAX_WIDTH) return fail(BD_EINVAL, who + ": n_out must be in 1..64 (a bank holds one-layer heads of the fused width)");
     for (int mb = 0; mb < n_members; ++mb) {
-        const std::string where = "bd_bank_create: member " + std::to_string(mb);
+        const std::string where = who + ": member " + std::to_string(mb);
         if (!layers[mb].kernel) return fail(BD_EINVAL, where + " has no kernel");
         if (layers[mb].n_in != BD_EMBEDDING_SIZE) return fail(BD_EINVAL, where + ": n_in must be 1024");
         if (layers[mb].n_out != C) return fail(BD_EINVAL, where + ": every member has the first member's n_out");
@@ -254,36 +201,24 @@ int bd_bank_create(int device, const bd_head_layer* layers, int32_t n_members, i
     const bool adam = opt->kind == BD_TRAIN_ADAM;
     bd::Shape s{n_members, C, bd::kGroupCols / C, 0, max_batch};
     s.groups = (n_members + s.mpg - 1) / s.mpg;
-    const int64_t slices = (max_batch + bd::kSliceRows - 1) / bd::kSliceRows;
-    auto up64 = [](int64_t v) { return (v + 63) / 64 * 64; };
     const int64_t block = s.groups * bd::kGroupFloats, zg = (int64_t)s.groups * max_batch * bd::kGroupCols;
-    const int64_t ws_floats = slices * block, rl = up64((int64_t)n_members * max_batch), acc_floats = up64(4 * (int64_t)n_members);
+    const int64_t ws_floats = bd::slices_of(max_batch) * block, rl = bd::up64((int64_t)n_members * max_batch),
+                  acc_floats = bd::up64(4 * (int64_t)n_members);
     const int64_t total = block * (adam ? 5 : 3) + 2 * zg + ws_floats + rl + acc_floats;
     if (total * (int64_t)sizeof(float) > BD_BANK_MAX_WORKSPACE_BYTES)
-        return fail(BD_EWORKSPACE, "bd_bank_create: " + std::to_string(n_members) + " members of " + std::to_string(C) + " outputs at max_batch " +
+        return fail(BD_EWORKSPACE, who + ": " + std::to_string(n_members) + " members of " + std::to_string(C) + " outputs at max_batch " +
                                        std::to_string(max_batch) + " need " + std::to_string(total * (int64_t)sizeof(float)) +
                                        " bytes, more than BD_BANK_MAX_WORKSPACE_BYTES; use fewer members or a smaller max_batch");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(BD_ENODEVICE, "bd_bank_create: no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= count) return fail(BD_ENODEVICE, "bd_bank_create: device index out of range");
-    hipDeviceProp_t prop;
-    BDB_HIP(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(BD_ENODEVICE, std::string("bd_bank_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
-    BDB_HIP(hipSetDevice(device));
+    if ((rc = bd::select_device(who, device)) < 0) return rc;
 
     std::unique_ptr<bd_bank_s> b(new bd_bank_s);
     b->device = device;
     b->loss = loss;
+    b->max_batch = max_batch;
     b->s = s;
     b->opt = *opt;
-    b->lr.assign(n_members, opt->learning_rate);
-    b->wd.assign(n_members, 0.0f);
-    b->frozen.assign(n_members, 0);
-    b->has_snapshot.assign(n_members, 0);
-    b->step.assign(n_members, 0);
-    BDB_HIP(hipMalloc(&b->pool, (size_t)total * sizeof(float)));
+    b->members.assign(n_members, opt->learning_rate);
+    BD_TRAIN_HIP(hipMalloc(&b->pool, (size_t)total * sizeof(float)));
     float* at = b->pool;
     auto take = [&at](int64_t n) {
         float* p = at;
@@ -305,45 +240,36 @@ int bd_bank_create(int device, const bd_head_layer* layers, int32_t n_members, i
     b->acc = reinterpret_cast<double*>(take(acc_floats));
     hipError_t err = hipMemset(b->pool, 0, (size_t)total * sizeof(float));
     for (int mb = 0; mb < n_members && err == hipSuccess; ++mb) {
-        const int group = mb / s.mpg, ng = (s.mpg < n_members - group * s.mpg ? s.mpg : n_members - group * s.mpg) * C;
-        float* dst = b->p + group * bd::kGroupFloats + (mb % s.mpg) * C;
-        err = hipMemcpy2D(dst, (size_t)ng * sizeof(float), layers[mb].kernel, (size_t)C * sizeof(float), (size_t)C * sizeof(float),
+        const bd::Columns c = bd::columns_of(s, mb);
+        float* dst = b->p + c.block + c.col0;
+        err = hipMemcpy2D(dst, (size_t)c.ng * sizeof(float), layers[mb].kernel, (size_t)C * sizeof(float), (size_t)C * sizeof(float),
                           bd::kIn, hipMemcpyHostToDevice);
         if (err == hipSuccess && layers[mb].bias)
-            err = hipMemcpy(dst + (size_t)bd::kIn * ng, layers[mb].bias, (size_t)C * sizeof(float), hipMemcpyHostToDevice);
+            err = hipMemcpy(dst + (size_t)bd::kIn * c.ng, layers[mb].bias, (size_t)C * sizeof(float), hipMemcpyHostToDevice);
     }
     if (err != hipSuccess) {
         (void)hipFree(b->pool);
-        return fail(BD_EHIP, std::string("bd_bank_create: ") + hipGetErrorString(err));
+        return fail(BD_EHIP, who + ": " + hipGetErrorString(err));
     }
     *out = b.release();
     return BD_OK;
 }
 
-int bd_bank_destroy(bd_bank b) {
-    if (!b) return BD_OK;
-    (void)hipSetDevice(b->device);
-    (void)hipStreamSynchronize(b->last);
-    if (b->pool) (void)hipFree(b->pool);
-    delete b;
-    return BD_OK;
-}
+int bd_bank_destroy(bd_bank b) { return bd::destroy(b); }
 
 int bd_bank_step(bd_bank b, const float* X, int64_t ldx, const int32_t* rows, const void* targets, const float* row_w, int64_t ldw,
                  int32_t B, void* stream_) {
     const char* who = "bd_bank_step";
     if (!b || !X || !targets) return fail(BD_EINVAL, std::string(who) + ": null argument");
-    int rc = bd::check_batch(b, X, ldx, B, who);
-    if (rc == BD_OK) rc = bd::check_weights(row_w, ldw, B, who);
+    int rc = bd::check_batch(who, b->max_batch, X, ldx, B);
+    if (rc == BD_OK) rc = bd::check_row_weights(who, row_w, ldw, B);
     if (rc < 0) return rc;
-    BDB_HIP(hipSetDevice(b->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    b->last = stream;
+    hipStream_t stream;
+    if ((rc = bd::enter(b, stream_, &stream)) < 0) return rc;
     const bd::Shape& s = b->s;
-    const int slices = (B + bd::kSliceRows - 1) / bd::kSliceRows;
-    const float inv = bd::inv_of(b, B);
-    for (int mb = 0; mb < s.M; ++mb)
-        if (!b->frozen[mb]) b->step[mb] += 1;
+    const int slices = bd::slices_of(B);
+    const float inv = bd::loss_inv(b->loss, B, s.C);
+    b->members.advance();
     if (row_w)
         hipLaunchKernelGGL(bd::bank_step_kernel<true>, dim3(slices, s.groups), dim3(512), 0, stream, X, ldx, rows, B, b->p, s, b->z, b->g,
                            b->loss, targets, row_w, ldw, inv, b->row_loss, b->ws);
@@ -352,13 +278,13 @@ int bd_bank_step(bd_bank b, const float* X, int64_t ldx, const int32_t* rows, co
                            b->loss, targets, row_w, ldw, inv, b->row_loss, b->ws);
     const int n = (bd::kIn + 1) * s.C;
     for (int first = 0; first < s.M; first += bd::kMembersPerLaunch) {
-        const bd::Members a = bd::members_of(b, first, s.M - first < bd::kMembersPerLaunch ? s.M - first : bd::kMembersPerLaunch);
-        hipLaunchKernelGGL(bd::bank_loss_sum_kernel, dim3(a.count), dim3(256), 0, stream, b->row_loss, B, s.max_batch, bd::scale_of(b, B),
-                           (float*)nullptr, b->acc, a);
+        const bd::Members a = b->members.launch_args(b->opt, first);
+        hipLaunchKernelGGL(bd::bank_loss_sum_kernel, dim3(a.count), dim3(256), 0, stream, b->row_loss, B, s.max_batch,
+                           bd::loss_scale(b->loss, B, s.C), (float*)nullptr, b->acc, a);
         hipLaunchKernelGGL(bd::bank_apply_kernel, dim3((n + 255) / 256, a.count), dim3(256), 0, stream, b->ws, slices, s, b->grad, b->p,
                            b->m, b->v, b->opt.kind, b->opt.beta_1, b->opt.beta_2, b->opt.epsilon, a);
     }
-    BDB_HIP(hipGetLastError());
+    BD_TRAIN_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -366,14 +292,13 @@ int bd_bank_loss(bd_bank b, const float* X, int64_t ldx, const int32_t* rows, co
                  int32_t B, float* loss_dev, void* stream_) {
     const char* who = "bd_bank_loss";
     if (!b || !X || !targets || !loss_dev) return fail(BD_EINVAL, std::string(who) + ": null argument");
-    int rc = bd::check_batch(b, X, ldx, B, who);
-    if (rc == BD_OK) rc = bd::check_weights(row_w, ldw, B, who);
+    int rc = bd::check_batch(who, b->max_batch, X, ldx, B);
+    if (rc == BD_OK) rc = bd::check_row_weights(who, row_w, ldw, B);
     if (rc < 0) return rc;
-    BDB_HIP(hipSetDevice(b->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    b->last = stream;
+    hipStream_t stream;
+    if ((rc = bd::enter(b, stream_, &stream)) < 0) return rc;
     const bd::Shape& s = b->s;
-    const float inv = bd::inv_of(b, B);
+    const float inv = bd::loss_inv(b->loss, B, s.C);
     hipLaunchKernelGGL(bd::bank_forward_kernel, dim3((B + 63) / 64, s.groups), dim3(256), 0, stream, X, ldx, rows, B, b->p, s, b->z,
                        (int64_t)s.max_batch * bd::kGroupCols, bd::kGroupCols);
     if (row_w)
@@ -383,13 +308,11 @@ int bd_bank_loss(bd_bank b, const float* X, int64_t ldx, const int32_t* rows, co
         hipLaunchKernelGGL(bd::bank_loss_rows_kernel<false>, dim3((B + 3) / 4, s.M), dim3(256), 0, stream, b->z, b->g, B, s, b->loss,
                            targets, row_w, ldw, inv, b->row_loss);
     for (int first = 0; first < s.M; first += bd::kMembersPerLaunch) {
-        bd::Members a{};
-        a.first = first;
-        a.count = s.M - first < bd::kMembersPerLaunch ? s.M - first : bd::kMembersPerLaunch;
-        hipLaunchKernelGGL(bd::bank_loss_sum_kernel, dim3(a.count), dim3(256), 0, stream, b->row_loss, B, s.max_batch, bd::scale_of(b, B),
-                           loss_dev, (double*)nullptr, a);
+        const bd::Members a = bd::members_from(s.M, first);
+        hipLaunchKernelGGL(bd::bank_loss_sum_kernel, dim3(a.count), dim3(256), 0, stream, b->row_loss, B, s.max_batch,
+                           bd::loss_scale(b->loss, B, s.C), loss_dev, (double*)nullptr, a);
     }
-    BDB_HIP(hipGetLastError());
+    BD_TRAIN_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -397,89 +320,49 @@ int bd_bank_forward(bd_bank b, const float* X, int64_t ldx, const int32_t* rows,
                     void* stream_) {
     const char* who = "bd_bank_forward";
     if (!b || !X || !logits_dev) return fail(BD_EINVAL, std::string(who) + ": null argument");
-    const int rc = bd::check_batch(b, X, ldx, B, who);
+    int rc = bd::check_batch(who, b->max_batch, X, ldx, B);
     if (rc < 0) return rc;
     const bd::Shape& s = b->s;
     if (ldl < (int64_t)s.M * s.C || ldl > INT32_MAX || (reinterpret_cast<uintptr_t>(logits_dev) & 3u))
         return fail(BD_EINVAL, std::string(who) + ": logits_dev must be float-aligned with ldl >= M C");
-    BDB_HIP(hipSetDevice(b->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    b->last = stream;
+    hipStream_t stream;
+    if ((rc = bd::enter(b, stream_, &stream)) < 0) return rc;
     // group g's columns are members g mpg ..: columns g mpg C .. of a row of the caller's matrix, side by side as in the group
     hipLaunchKernelGGL(bd::bank_forward_kernel, dim3((B + 63) / 64, s.groups), dim3(256), 0, stream, X, ldx, rows, B, b->p, s, logits_dev,
                        (int64_t)s.mpg * s.C, (int)ldl);
-    BDB_HIP(hipGetLastError());
+    BD_TRAIN_HIP(hipGetLastError());
     return BD_OK;
 }
 
 int bd_bank_set_learning_rate(bd_bank b, int32_t member, float learning_rate) {
-    const int rc = bd::check_member(b, member, "bd_bank_set_learning_rate");
-    if (rc < 0) return rc;
-    if (!(learning_rate > 0.0f) || !std::isfinite(learning_rate))
-        return fail(BD_EINVAL, "bd_bank_set_learning_rate: learning_rate must be positive and finite");
-    b->lr[member] = learning_rate;
-    return BD_OK;
+    return bd::set_learning_rate(b, member, learning_rate, "bd_bank_set_learning_rate");
 }
 
 int bd_bank_set_weight_decay(bd_bank b, int32_t member, float weight_decay) {
-    const int rc = bd::check_member(b, member, "bd_bank_set_weight_decay");
-    if (rc < 0) return rc;
-    if (!(weight_decay >= 0.0f) || !std::isfinite(weight_decay))
-        return fail(BD_EINVAL, "bd_bank_set_weight_decay: weight_decay must be finite and not negative");
-    b->wd[member] = weight_decay;
-    return BD_OK;
+    return bd::set_weight_decay(b, member, weight_decay, "bd_bank_set_weight_decay");
 }
 
-int bd_bank_set_frozen(bd_bank b, int32_t member, int32_t frozen) {
-    const int rc = bd::check_member(b, member, "bd_bank_set_frozen");
-    if (rc < 0) return rc;
-    if (frozen != 0 && frozen != 1) return fail(BD_EINVAL, "bd_bank_set_frozen: frozen must be 0 or 1");
-    b->frozen[member] = frozen;
-    return BD_OK;
-}
-
-// member's columns of the parameters -> its columns of the snapshot (to_snapshot) or back, on the caller's stream
-static int copy_member(bd_bank b, int32_t member, bool to_snapshot, void* stream_) {
-    BDB_HIP(hipSetDevice(b->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    b->last = stream;
-    const bd::Shape& s = b->s;
-    const int group = member / s.mpg, nm = s.mpg < s.M - group * s.mpg ? s.mpg : s.M - group * s.mpg;
-    float *p = b->p + group * bd::kGroupFloats, *snap = b->snap + group * bd::kGroupFloats;
-    hipLaunchKernelGGL(bd::bank_copy_member_kernel, dim3(((bd::kIn + 1) * s.C + 255) / 256), dim3(256), 0, stream, to_snapshot ? snap : p,
-                       to_snapshot ? p : snap, s.C, nm * s.C, (member % s.mpg) * s.C);
-    BDB_HIP(hipGetLastError());
-    return BD_OK;
-}
+int bd_bank_set_frozen(bd_bank b, int32_t member, int32_t frozen) { return bd::set_frozen(b, member, frozen, "bd_bank_set_frozen"); }
 
 int bd_bank_snapshot(bd_bank b, int32_t member, void* stream) {
-    int rc = bd::check_member(b, member, "bd_bank_snapshot");
-    if (rc < 0) return rc;
-    rc = copy_member(b, member, true, stream);
-    if (rc == BD_OK) b->has_snapshot[member] = 1;
-    return rc;
+    return bd::snapshot_member(b, member, stream, "bd_bank_snapshot", bd::copy_member);
 }
 
 int bd_bank_restore(bd_bank b, int32_t member, void* stream) {
-    const int rc = bd::check_member(b, member, "bd_bank_restore");
-    if (rc < 0) return rc;
-    if (!b->has_snapshot[member])
-        return fail(BD_EINVAL, "bd_bank_restore: no snapshot of member " + std::to_string(member) + " was taken (bd_bank_snapshot)");
-    return copy_member(b, member, false, stream);
+    return bd::restore_member(b, member, stream, "bd_bank_restore", "bd_bank_snapshot", bd::copy_member);
 }
 
 static int read_pair(bd_bank b, int32_t member, bool grad, float* w_host, float* b_host, const char* who) {
-    const int rc = bd::check_member(b, member, who);
+    int rc = bd::check_member(b, member, who);
+    if (rc == BD_OK) rc = bd::enter_and_wait(b);
     if (rc < 0) return rc;
-    BDB_HIP(hipSetDevice(b->device));
-    BDB_HIP(hipStreamSynchronize(b->last));
     const bd::Shape& s = b->s;
-    const int group = member / s.mpg, ng = (s.mpg < s.M - group * s.mpg ? s.mpg : s.M - group * s.mpg) * s.C;
-    const float* src = (grad ? b->grad : b->p) + group * bd::kGroupFloats + (member % s.mpg) * s.C;
+    const bd::Columns c = bd::columns_of(s, member);
+    const float* src = (grad ? b->grad : b->p) + c.block + c.col0;
     if (w_host)
-        BDB_HIP(hipMemcpy2D(w_host, (size_t)s.C * sizeof(float), src, (size_t)ng * sizeof(float), (size_t)s.C * sizeof(float), bd::kIn,
-                            hipMemcpyDeviceToHost));
-    if (b_host) BDB_HIP(hipMemcpy(b_host, src + (size_t)bd::kIn * ng, (size_t)s.C * sizeof(float), hipMemcpyDeviceToHost));
+        BD_TRAIN_HIP(hipMemcpy2D(w_host, (size_t)s.C * sizeof(float), src, (size_t)c.ng * sizeof(float), (size_t)s.C * sizeof(float),
+                                 bd::kIn, hipMemcpyDeviceToHost));
+    if (b_host) BD_TRAIN_HIP(hipMemcpy(b_host, src + (size_t)bd::kIn * c.ng, (size_t)s.C * sizeof(float), hipMemcpyDeviceToHost));
     return BD_OK;
 }
 
@@ -491,37 +374,14 @@ int bd_bank_gradients(bd_bank b, int32_t member, float* dW_host, float* db_host)
     return read_pair(b, member, true, dW_host, db_host, "bd_bank_gradients");
 }
 
-int bd_bank_mean_loss(bd_bank b, int32_t reset, float* mean_host) {
-    if (!b || !mean_host) return fail(BD_EINVAL, "bd_bank_mean_loss: null argument");
-    BDB_HIP(hipSetDevice(b->device));
-    BDB_HIP(hipStreamSynchronize(b->last));
-    std::vector<double> acc(2 * (size_t)b->s.M, 0.0);
-    BDB_HIP(hipMemcpy(acc.data(), b->acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int mb = 0; mb < b->s.M; ++mb) mean_host[mb] = acc[2 * mb + 1] > 0.0 ? (float)(acc[2 * mb] / acc[2 * mb + 1]) : 0.0f;
-    if (reset) BDB_HIP(hipMemset(b->acc, 0, acc.size() * sizeof(double)));
-    return BD_OK;
-}
+int bd_bank_mean_loss(bd_bank b, int32_t reset, float* mean_host) { return bd::mean_losses(b, reset, mean_host, "bd_bank_mean_loss"); }
 
-int64_t bd_bank_workspace_floats(bd_bank b) {
-    if (!b) return fail(BD_EINVAL, "bd_bank_workspace_floats: null handle");
-    return b->ws_floats;
-}
+int64_t bd_bank_workspace_floats(bd_bank b) { return bd::workspace_floats(b, "bd_bank_workspace_floats"); }
 
-int bd_bank_workspace_fill(bd_bank b, uint32_t pattern) {
-    if (!b) return fail(BD_EINVAL, "bd_bank_workspace_fill: null handle");
-    BDB_HIP(hipSetDevice(b->device));
-    BDB_HIP(hipStreamSynchronize(b->last));
-    BDB_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b->ws), (int)pattern, (size_t)b->ws_floats));
-    BDB_HIP(hipDeviceSynchronize());
-    return BD_OK;
-}
+int bd_bank_workspace_fill(bd_bank b, uint32_t pattern) { return bd::workspace_fill(b, pattern, "bd_bank_workspace_fill"); }
 
 int bd_bank_workspace_read(bd_bank b, float* host, int64_t floats) {
-    if (!b || !host || floats < 0 || floats > b->ws_floats) return fail(BD_EINVAL, "bd_bank_workspace_read: bad argument");
-    BDB_HIP(hipSetDevice(b->device));
-    BDB_HIP(hipStreamSynchronize(b->last));
-    BDB_HIP(hipMemcpy(host, b->ws, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost));
-    return BD_OK;
+    return bd::workspace_read(b, host, floats, "bd_bank_workspace_read");
 }
 
 }  // extern "C"

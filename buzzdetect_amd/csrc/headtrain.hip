@@ -1,9 +1,12 @@
 // The classifier-head trainer (include/buzzdetect_train.h): forward, loss, backward and update of a Dense stack on
 // embeddings, in exact float32 on v_mfma_f32_32x32x2_f32.
 //
-//
-// The device routines - mma_chain and the tiles built on it, loss_row, the partials' sum and the update - live in
-// headtrain_device.h, which headbank.hip includes too.  What differs between the three products is where a lane finds its operands:
+// This file: the trainer's kernels, its pool (a Dense stack's pieces as headtrain_host.h lays them out, then the workspace, the
+// rows' losses and the running loss) and the launches of its entry points.  The device routines - mma_chain and the tiles
+// built on it, loss_row, the partials' sum and the update - live in headtrain_device.h, and the host side the three training
+// families share - the checks, the trainer's rate, decay, snapshot flag and step count (a MemberState of one member), the
+// bias-corrected Adam rate, the stack's layout, the running loss and the workspace's test hooks - in headtrain_host.h;
+// headbank.hip and stackbank.hip include both too.  The three matrix products differ in where a lane finds its operands:
 //   forward  Y = act(A W + b)      reduce over n_in    A: 16 bytes of a row (row rows[r] of X for layer 0)   B: W[k][col]
 //   dA       G' = (G W^T) * act'   reduce over n_out   A: 16 bytes of a row of G                             B: W[col][k]
 //   dW       P_s = A^T G           reduce over the rows of slice s   A: A[row][col]                          B: G[row][col]
@@ -24,18 +27,10 @@
 // barriers.  Decoupled weight decay is apply_kernel's: p = p - (lr wd) p on a layer's kernel elements (never its bias), two
 // roundings, before the optimizer's update is subtracted from p.
 #include "headtrain_device.h"
-
-#include <cstring>
-#include <memory>
-#include <string>
+#include "headtrain_host.h"
 
 namespace bd {
-
-void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
-
 namespace {
-
-using namespace train;
 
 // ---- kernels ----
 
@@ -124,88 +119,56 @@ __global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ ws
     apply_element(sum_partials(ws + i, slices, (size_t)n), (size_t)i, i < u.decay_n, grad, P, m, v, u);
 }
 
-__global__ void fill_kernel(uint32_t* p, size_t n, uint32_t pattern) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = pattern;
-}
-
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
-#define BDT_HIP(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(BD_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-struct Layer {
-    int k, n, act, ld;              // ld = round_up(n, 32): row stride of y and g
-    float *p, *grad, *m, *v;        // [k n + n] each: W then b (m, v: Adam only)
-    float* snap;                    // [k n + n]: the parameters as bd_trainer_snapshot found them
-    float *y, *g;                   // [max_batch][ld]: activations (the last layer's: logits) and d loss / d pre-activation
-};
-
 }  // namespace
 }  // namespace bd
 
-struct bd_trainer_s {
-    int device = 0, n_layers = 0, loss = 0, max_batch = 0;
-    bd_train_optimizer opt{};
-    int64_t step = 0;
+struct bd_trainer_s : bd::TrainHandle {     // members: the one of this trainer (its rate, decay, snapshot flag and step count)
+    bd::StackLayout s;              // offsets into pool
     bool fused = true;
-    float weight_decay = 0.0f;
-    bool has_snapshot = false;
-    bd::Layer layers[BD_HEAD_MAX_LAYERS]{};
-    float* pool = nullptr;          // one allocation behind every pointer above and below
-    float* ws = nullptr;            // [slices][k n + n] of the layer at work
-    int64_t ws_floats = 0;
     float* row_loss = nullptr;      // [max_batch]
-    double* acc = nullptr;          // running loss sum, rows
-    hipStream_t last = nullptr;
+    // ws: [slices][k n + n] of the layer at work
 };
 
 namespace bd {
 namespace {
 
-bool fusable(const bd_trainer_s* t) { return t->n_layers == 1 && t->layers[0].n <= BD_TRAIN_FUSED_MAX_WIDTH; }
+bool fusable(const bd_trainer_s* t) { return t->s.n_layers == 1 && t->s.layers[0].n <= BD_TRAIN_FUSED_MAX_WIDTH; }
 
-int check_batch(const bd_trainer_s* t, const float* X, int64_t ldx, const void* targets, int32_t B, const char* who) {
+// what every step and loss call checks, in this order
+int check_call(const bd_trainer_s* t, const float* X, int64_t ldx, const void* targets, const float* row_w, int32_t B, const char* who) {
     if (!t || !X || !targets) return fail(BD_EINVAL, std::string(who) + ": null argument");
-    if (B < 1 || B > t->max_batch) return fail(BD_EINVAL, std::string(who) + ": B must be in 1..max_batch");
-    if (ldx < BD_EMBEDDING_SIZE || ldx % 4 || (reinterpret_cast<uintptr_t>(X) & 15u))
-        return fail(BD_EINVAL, std::string(who) + ": X needs 16-byte alignment and ldx >= 1024, a multiple of 4");
-    return BD_OK;
+    const int rc = check_batch(who, t->max_batch, X, ldx, B);
+    return rc < 0 ? rc : check_row_weights(who, row_w, B, B);
 }
 
 void enqueue_forward(bd_trainer_s* t, const float* X, int64_t ldx, const int* rows, int B, hipStream_t stream) {
     const float* a = X;
     int64_t lda = ldx;
-    for (int l = 0; l < t->n_layers; ++l) {
-        const Layer& L = t->layers[l];
-        const int act = l + 1 < t->n_layers ? L.act : BD_HEAD_LINEAR;
+    for (int l = 0; l < t->s.n_layers; ++l) {
+        const StackLayer& L = t->s.layers[l];
+        const int act = l + 1 < t->s.n_layers ? L.act : BD_HEAD_LINEAR;
         hipLaunchKernelGGL(forward_kernel, dim3((B + 63) / 64, (L.n + 63) / 64), dim3(256), 0, stream, a, lda, l == 0 ? rows : nullptr,
-                           B, L.k, L.p, L.n, act, L.y, L.ld);
-        a = L.y;
+                           B, L.k, t->pool + L.p, L.n, act, t->pool + L.y, L.ld);
+        a = t->pool + L.y;
         lda = L.ld;
     }
 }
 
 void enqueue_loss(bd_trainer_s* t, const void* targets, const float* row_w, int B, float* loss_dev, bool accumulate, bool rows_done,
                   hipStream_t stream) {
-    const Layer& L = t->layers[t->n_layers - 1];
-    const bool binary = t->loss == BD_TRAIN_BINARY;
+    const StackLayer& L = t->s.last();
+    float *y = t->pool + L.y, *g = t->pool + L.g;
     if (!rows_done) {
-        const float inv = 1.0f / (binary ? (float)B * (float)L.n : (float)B);
+        const float inv = loss_inv(t->loss, B, L.n);
         if (row_w)
-            hipLaunchKernelGGL(loss_rows_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, stream, L.y, L.g, L.ld, B, L.n, t->loss,
-                               targets, row_w, inv, t->row_loss);
+            hipLaunchKernelGGL(loss_rows_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, stream, y, g, L.ld, B, L.n, t->loss, targets,
+                               row_w, inv, t->row_loss);
         else
-            hipLaunchKernelGGL(loss_rows_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, stream, L.y, L.g, L.ld, B, L.n, t->loss,
-                               targets, row_w, inv, t->row_loss);
+            hipLaunchKernelGGL(loss_rows_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, stream, y, g, L.ld, B, L.n, t->loss, targets,
+                               row_w, inv, t->row_loss);
     }
-    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, stream, t->row_loss, B, 1.0 / (binary ? (double)B * L.n : (double)B),
-                       loss_dev, accumulate ? t->acc : nullptr);
+    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, stream, t->row_loss, B, loss_scale(t->loss, B, L.n), loss_dev,
+                       accumulate ? t->acc : nullptr);
 }
 
 }  // namespace
@@ -219,88 +182,32 @@ int bd_train_abi_version(void) { return BD_TRAIN_ABI_VERSION; }
 
 int bd_trainer_create(int device, const bd_head_layer* layers, int32_t n_layers, int32_t loss, const bd_train_optimizer* opt,
                       int32_t max_batch, bd_trainer* out) {
-    if (!out || !layers || !opt) return fail(BD_EINVAL, "bd_trainer_create: null argument");
+    const std::string who = "bd_trainer_create";
+    if (!out || !layers || !opt) return fail(BD_EINVAL, who + ": null argument");
     *out = nullptr;
-    if (n_layers < 1 || n_layers > BD_HEAD_MAX_LAYERS) return fail(BD_EINVAL, "bd_trainer_create: n_layers must be in 1..8");
-    if (loss != BD_TRAIN_CATEGORICAL && loss != BD_TRAIN_BINARY) return fail(BD_EINVAL, "bd_trainer_create: unknown loss");
-    if (opt->kind != BD_TRAIN_SGD && opt->kind != BD_TRAIN_ADAM) return fail(BD_EINVAL, "bd_trainer_create: unknown optimizer");
-    if (!(opt->learning_rate > 0.0f) || !std::isfinite(opt->learning_rate))
-        return fail(BD_EINVAL, "bd_trainer_create: learning_rate must be positive and finite");
-    if (opt->kind == BD_TRAIN_ADAM && !(opt->beta_1 >= 0.0f && opt->beta_1 < 1.0f && opt->beta_2 >= 0.0f && opt->beta_2 < 1.0f &&
-                                        opt->epsilon > 0.0f))
-        return fail(BD_EINVAL, "bd_trainer_create: Adam needs 0 <= beta < 1 and epsilon > 0");
-    if (max_batch < 1 || max_batch > BD_TRAIN_MAX_BATCH) return fail(BD_EINVAL, "bd_trainer_create: max_batch must be in 1..65536");
-    for (int l = 0; l < n_layers; ++l) {
-        const bd_head_layer& L = layers[l];
-        const std::string where = "bd_trainer_create: layer " + std::to_string(l);
-        if (!L.kernel) return fail(BD_EINVAL, where + " has no kernel");
-        if (L.n_in != (l == 0 ? BD_EMBEDDING_SIZE : layers[l - 1].n_out))
-            return fail(BD_EINVAL, where + ": n_in must be 1024 for the first layer, the width before it for the others");
-        if (L.n_out < 1 || L.n_out > BD_HEAD_MAX_WIDTH) return fail(BD_EINVAL, where + ": n_out must be in 1..2048");
-        if (L.activation < BD_HEAD_LINEAR || L.activation > BD_HEAD_SOFTMAX || (L.activation == BD_HEAD_SOFTMAX && l + 1 < n_layers))
-            return fail(BD_EINVAL, where + ": hidden activations are linear, relu, sigmoid or tanh");
-    }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(BD_ENODEVICE, "bd_trainer_create: no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= count) return fail(BD_ENODEVICE, "bd_trainer_create: device index out of range");
-    hipDeviceProp_t prop;
-    BDT_HIP(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(BD_ENODEVICE, std::string("bd_trainer_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
-    BDT_HIP(hipSetDevice(device));
+    if (n_layers < 1 || n_layers > BD_HEAD_MAX_LAYERS) return fail(BD_EINVAL, who + ": n_layers must be in 1..8");
+    int rc = bd::check_training_setup(who, loss, opt, max_batch);
+    if (rc == BD_OK) rc = bd::check_stack(who + ": layer ", layers, n_layers);
+    if (rc == BD_OK) rc = bd::select_device(who, device);
+    if (rc < 0) return rc;
 
     std::unique_ptr<bd_trainer_s> t(new bd_trainer_s);
     t->device = device;
-    t->n_layers = n_layers;
     t->loss = loss;
     t->max_batch = max_batch;
     t->opt = *opt;
-    const bool adam = opt->kind == BD_TRAIN_ADAM;
-    const int64_t slices = (max_batch + bd::kSliceRows - 1) / bd::kSliceRows;
-    // lay the pool out in floats, every piece on a 64-float boundary
-    auto up64 = [](int64_t v) { return (v + 63) / 64 * 64; };
-    int64_t total = 0, params_max = 0;
-    int64_t off_p[BD_HEAD_MAX_LAYERS], off_y[BD_HEAD_MAX_LAYERS];
-    for (int l = 0; l < n_layers; ++l) {
-        bd::Layer& L = t->layers[l];
-        L.k = layers[l].n_in;
-        L.n = layers[l].n_out;
-        L.act = layers[l].activation;
-        L.ld = (L.n + 31) / 32 * 32;
-        const int64_t np = (int64_t)L.k * L.n + L.n;
-        params_max = np > params_max ? np : params_max;
-        off_p[l] = total;
-        total += up64(np) * (adam ? 5 : 3);
-        off_y[l] = total;
-        total += up64((int64_t)max_batch * L.ld) * 2;
-    }
-    const int64_t off_ws = total;
-    t->ws_floats = slices * params_max;
-    total += up64(t->ws_floats);
-    const int64_t off_rl = total;
-    total += up64(max_batch);
-    const int64_t off_acc = total;
-    total += 64;
-    BDT_HIP(hipMalloc(&t->pool, (size_t)total * sizeof(float)));
+    t->members.assign(1, opt->learning_rate);
+    t->s = bd::stack_layout(layers, n_layers, opt->kind == BD_TRAIN_ADAM, max_batch);
+    // behind the layers: the workspace, the rows' losses, the running loss
+    t->ws_floats = bd::slices_of(max_batch) * t->s.params_max;
+    const int64_t off_ws = t->s.floats, off_rl = off_ws + bd::up64(t->ws_floats), off_acc = off_rl + bd::up64(max_batch);
+    const int64_t total = off_acc + 64;
+    BD_TRAIN_HIP(hipMalloc(&t->pool, (size_t)total * sizeof(float)));
     hipError_t err = hipMemset(t->pool, 0, (size_t)total * sizeof(float));
-    for (int l = 0; l < n_layers && err == hipSuccess; ++l) {
-        bd::Layer& L = t->layers[l];
-        const int64_t np = (int64_t)L.k * L.n + L.n, step = up64(np);
-        L.p = t->pool + off_p[l];
-        L.grad = L.p + step;
-        L.m = adam ? L.p + 2 * step : nullptr;
-        L.v = adam ? L.p + 3 * step : nullptr;
-        L.snap = L.p + (adam ? 4 : 2) * step;
-        L.y = t->pool + off_y[l];
-        L.g = L.y + up64((int64_t)max_batch * L.ld);
-        err = hipMemcpy(L.p, layers[l].kernel, (size_t)L.k * L.n * sizeof(float), hipMemcpyHostToDevice);
-        if (err == hipSuccess && layers[l].bias)
-            err = hipMemcpy(L.p + (size_t)L.k * L.n, layers[l].bias, (size_t)L.n * sizeof(float), hipMemcpyHostToDevice);
-    }
+    if (err == hipSuccess) err = bd::upload_stack(t->pool, t->s, layers);
     if (err != hipSuccess) {
         (void)hipFree(t->pool);
-        return fail(BD_EHIP, std::string("bd_trainer_create: ") + hipGetErrorString(err));
+        return fail(BD_EHIP, who + ": " + hipGetErrorString(err));
     }
     t->ws = t->pool + off_ws;
     t->row_loss = t->pool + off_rl;
@@ -309,14 +216,7 @@ int bd_trainer_create(int device, const bd_head_layer* layers, int32_t n_layers,
     return BD_OK;
 }
 
-int bd_trainer_destroy(bd_trainer t) {
-    if (!t) return BD_OK;
-    (void)hipSetDevice(t->device);
-    (void)hipStreamSynchronize(t->last);
-    if (t->pool) (void)hipFree(t->pool);
-    delete t;
-    return BD_OK;
-}
+int bd_trainer_destroy(bd_trainer t) { return bd::destroy(t); }
 
 int bd_trainer_set_fusion(bd_trainer t, int32_t fused) {
     if (!t) return fail(BD_EINVAL, "bd_trainer_set_fusion: null handle");
@@ -327,53 +227,48 @@ int bd_trainer_set_fusion(bd_trainer t, int32_t fused) {
 // bd_trainer_step (row_w == nullptr: the plain kernels) and bd_trainer_step_weighted
 static int do_step(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, const float* row_w, int32_t B,
                    void* stream_, const char* who) {
-    const int rc = bd::check_batch(t, X, ldx, targets, B, who);
+    int rc = bd::check_call(t, X, ldx, targets, row_w, B, who);
     if (rc < 0) return rc;
-    if (reinterpret_cast<uintptr_t>(row_w) & 3u) return fail(BD_EINVAL, std::string(who) + ": row_weights is not aligned to a float");
-    BDT_HIP(hipSetDevice(t->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    t->last = stream;
-    const int slices = (B + bd::kSliceRows - 1) / bd::kSliceRows;
-    const bool binary = t->loss == BD_TRAIN_BINARY;
-    t->step += 1;
-    bd::Update u{t->opt.kind, t->opt.learning_rate, t->opt.beta_1, t->opt.beta_2, t->opt.epsilon, 0.0f,
-                 t->weight_decay != 0.0f ? t->opt.learning_rate * t->weight_decay : 0.0f, 0};
-    if (u.kind == BD_TRAIN_ADAM)
-        u.lr_t = (float)((double)u.lr * std::sqrt(1.0 - std::pow((double)u.b2, (double)t->step)) /
-                         (1.0 - std::pow((double)u.b1, (double)t->step)));
+    hipStream_t stream;
+    if ((rc = bd::enter(t, stream_, &stream)) < 0) return rc;
+    const int slices = bd::slices_of(B);
+    t->members.advance();
+    bd::Update u = t->members.update_of(t->opt, 0);
+    float* pool = t->pool;
     const bool fused = t->fused && bd::fusable(t);
     if (fused) {
-        const bd::Layer& L = t->layers[0];
-        const float inv = 1.0f / (binary ? (float)B * (float)L.n : (float)B);
+        const bd::StackLayer& L = t->s.layers[0];
+        const float inv = bd::loss_inv(t->loss, B, L.n);
         if (row_w)
-            hipLaunchKernelGGL(bd::fused_step_kernel<true>, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, L.p, L.n, L.y,
-                               L.g, L.ld, t->loss, targets, row_w, inv, t->row_loss, t->ws);
+            hipLaunchKernelGGL(bd::fused_step_kernel<true>, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, pool + L.p, L.n,
+                               pool + L.y, pool + L.g, L.ld, t->loss, targets, row_w, inv, t->row_loss, t->ws);
         else
-            hipLaunchKernelGGL(bd::fused_step_kernel<false>, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, L.p, L.n, L.y,
-                               L.g, L.ld, t->loss, targets, row_w, inv, t->row_loss, t->ws);
+            hipLaunchKernelGGL(bd::fused_step_kernel<false>, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, pool + L.p, L.n,
+                               pool + L.y, pool + L.g, L.ld, t->loss, targets, row_w, inv, t->row_loss, t->ws);
     } else {
         bd::enqueue_forward(t, X, ldx, rows, B, stream);
     }
     bd::enqueue_loss(t, targets, row_w, B, nullptr, true, fused, stream);
-    for (int l = t->n_layers - 1; l >= 0; --l) {
-        const bd::Layer& L = t->layers[l];
+    for (int l = t->s.n_layers - 1; l >= 0; --l) {
+        const bd::StackLayer& L = t->s.layers[l];
         const int n = L.k * L.n + L.n;
         if (!fused) {
-            const float* a = l == 0 ? X : t->layers[l - 1].y;
-            const int64_t lda = l == 0 ? ldx : t->layers[l - 1].ld;
+            const float* a = l == 0 ? X : pool + t->s.layers[l - 1].y;
+            const int64_t lda = l == 0 ? ldx : t->s.layers[l - 1].ld;
             const int tiles = (L.k + 31) / 32 * ((L.n + 31) / 32);
             hipLaunchKernelGGL(bd::weight_grad_kernel, dim3((tiles + 3) / 4, slices), dim3(256), 0, stream, a, lda,
-                               l == 0 ? rows : nullptr, B, L.k, L.g, L.ld, L.n, t->ws);
+                               l == 0 ? rows : nullptr, B, L.k, pool + L.g, L.ld, L.n, t->ws);
         }
         if (l > 0) {                                     // with this layer's weights as the forward pass saw them
-            const bd::Layer& Lp = t->layers[l - 1];
-            hipLaunchKernelGGL(bd::input_grad_kernel, dim3((B + 63) / 64, (L.k + 63) / 64), dim3(256), 0, stream, L.g, L.ld, B, L.k,
-                               L.p, L.n, Lp.y, Lp.act, Lp.g, Lp.ld);
+            const bd::StackLayer& Lp = t->s.layers[l - 1];
+            hipLaunchKernelGGL(bd::input_grad_kernel, dim3((B + 63) / 64, (L.k + 63) / 64), dim3(256), 0, stream, pool + L.g, L.ld, B,
+                               L.k, pool + L.p, L.n, pool + Lp.y, Lp.act, pool + Lp.g, Lp.ld);
         }
         u.decay_n = L.k * L.n;
-        hipLaunchKernelGGL(bd::apply_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, t->ws, slices, n, L.grad, L.p, L.m, L.v, u);
+        hipLaunchKernelGGL(bd::apply_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, t->ws, slices, n, pool + L.grad, pool + L.p,
+                           bd::slot(pool, L.m), bd::slot(pool, L.v), u);
     }
-    BDT_HIP(hipGetLastError());
+    BD_TRAIN_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -388,16 +283,14 @@ int bd_trainer_step_weighted(bd_trainer t, const float* X, int64_t ldx, const in
 
 static int do_loss(bd_trainer t, const float* X, int64_t ldx, const int32_t* rows, const void* targets, const float* row_w, int32_t B,
                    float* loss_dev, void* stream_, const char* who) {
-    const int rc = bd::check_batch(t, X, ldx, targets, B, who);
+    int rc = bd::check_call(t, X, ldx, targets, row_w, B, who);
     if (rc < 0) return rc;
-    if (reinterpret_cast<uintptr_t>(row_w) & 3u) return fail(BD_EINVAL, std::string(who) + ": row_weights is not aligned to a float");
     if (!loss_dev) return fail(BD_EINVAL, std::string(who) + ": null loss_dev");
-    BDT_HIP(hipSetDevice(t->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    t->last = stream;
+    hipStream_t stream;
+    if ((rc = bd::enter(t, stream_, &stream)) < 0) return rc;
     bd::enqueue_forward(t, X, ldx, rows, B, stream);
     bd::enqueue_loss(t, targets, row_w, B, loss_dev, false, false, stream);
-    BDT_HIP(hipGetLastError());
+    BD_TRAIN_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -412,56 +305,36 @@ int bd_trainer_loss_weighted(bd_trainer t, const float* X, int64_t ldx, const in
 }
 
 int bd_trainer_set_weight_decay(bd_trainer t, float weight_decay) {
-    if (!t) return fail(BD_EINVAL, "bd_trainer_set_weight_decay: null handle");
-    if (!(weight_decay >= 0.0f) || !std::isfinite(weight_decay))
-        return fail(BD_EINVAL, "bd_trainer_set_weight_decay: weight_decay must be finite and not negative");
-    t->weight_decay = weight_decay;
-    return BD_OK;
+    return bd::set_weight_decay(t, 0, weight_decay, "bd_trainer_set_weight_decay");
 }
 
 int bd_trainer_set_learning_rate(bd_trainer t, float learning_rate) {
-    if (!t) return fail(BD_EINVAL, "bd_trainer_set_learning_rate: null handle");
-    if (!(learning_rate > 0.0f) || !std::isfinite(learning_rate))
-        return fail(BD_EINVAL, "bd_trainer_set_learning_rate: learning_rate must be positive and finite");
-    t->opt.learning_rate = learning_rate;
-    return BD_OK;
+    return bd::set_learning_rate(t, 0, learning_rate, "bd_trainer_set_learning_rate");
 }
 
-// parameters -> snapshot (to_snapshot) or back, layer by layer, on the caller's stream
+// parameters -> snapshot (to_snapshot) or back, on the caller's stream
 static int copy_parameters(bd_trainer t, bool to_snapshot, void* stream_) {
-    BDT_HIP(hipSetDevice(t->device));
-    hipStream_t stream = (hipStream_t)stream_;
-    t->last = stream;
-    for (int l = 0; l < t->n_layers; ++l) {
-        const bd::Layer& L = t->layers[l];
-        const size_t bytes = ((size_t)L.k * L.n + L.n) * sizeof(float);
-        BDT_HIP(hipMemcpyAsync(to_snapshot ? L.snap : L.p, to_snapshot ? L.p : L.snap, bytes, hipMemcpyDeviceToDevice, stream));
-    }
-    return BD_OK;
+    hipStream_t stream;
+    const int rc = bd::enter(t, stream_, &stream);
+    return rc < 0 ? rc : bd::copy_stack(t->pool, t->s, to_snapshot, stream);
 }
 
 int bd_trainer_snapshot(bd_trainer t, void* stream) {
     if (!t) return fail(BD_EINVAL, "bd_trainer_snapshot: null handle");
     const int rc = copy_parameters(t, true, stream);
-    if (rc == BD_OK) t->has_snapshot = true;
+    if (rc == BD_OK) t->members.has_snapshot[0] = 1;
     return rc;
 }
 
 int bd_trainer_restore(bd_trainer t, void* stream) {
     if (!t) return fail(BD_EINVAL, "bd_trainer_restore: null handle");
-    if (!t->has_snapshot) return fail(BD_EINVAL, "bd_trainer_restore: no snapshot was taken (bd_trainer_snapshot)");
+    if (!t->members.has_snapshot[0]) return fail(BD_EINVAL, "bd_trainer_restore: no snapshot was taken (bd_trainer_snapshot)");
     return copy_parameters(t, false, stream);
 }
 
 static int read_pair(bd_trainer t, int32_t layer, bool grad, float* w_host, float* b_host, const char* who) {
-    if (!t || layer < 0 || layer >= t->n_layers) return fail(BD_EINVAL, std::string(who) + ": no such layer");
-    BDT_HIP(hipSetDevice(t->device));
-    BDT_HIP(hipStreamSynchronize(t->last));
-    const bd::Layer& L = t->layers[layer];
-    const float* src = grad ? L.grad : L.p;
-    if (w_host) BDT_HIP(hipMemcpy(w_host, src, (size_t)L.k * L.n * sizeof(float), hipMemcpyDeviceToHost));
-    if (b_host) BDT_HIP(hipMemcpy(b_host, src + (size_t)L.k * L.n, (size_t)L.n * sizeof(float), hipMemcpyDeviceToHost));
-    return BD_OK;
+    if (!t || layer < 0 || layer >= t->s.n_layers) return fail(BD_EINVAL, std::string(who) + ": no such layer");
+    return bd::read_stack_pair(t, t->pool, t->s.layers[layer], grad, w_host, b_host);
 }
 
 int bd_trainer_gradients(bd_trainer t, int32_t layer, float* dW_host, float* db_host) {
@@ -474,47 +347,24 @@ int bd_trainer_read(bd_trainer t, int32_t layer, float* kernel_host, float* bias
 
 int bd_trainer_logits(bd_trainer t, int32_t B, float* logits_host) {
     if (!t || !logits_host || B < 1 || B > t->max_batch) return fail(BD_EINVAL, "bd_trainer_logits: bad argument");
-    BDT_HIP(hipSetDevice(t->device));
-    BDT_HIP(hipStreamSynchronize(t->last));
-    const bd::Layer& L = t->layers[t->n_layers - 1];
-    BDT_HIP(hipMemcpy2D(logits_host, (size_t)L.n * sizeof(float), L.y, (size_t)L.ld * sizeof(float), (size_t)L.n * sizeof(float), B,
-                        hipMemcpyDeviceToHost));
+    const int rc = bd::enter_and_wait(t);
+    if (rc < 0) return rc;
+    const bd::StackLayer& L = t->s.last();
+    BD_TRAIN_HIP(hipMemcpy2D(logits_host, (size_t)L.n * sizeof(float), t->pool + L.y, (size_t)L.ld * sizeof(float),
+                        (size_t)L.n * sizeof(float), B, hipMemcpyDeviceToHost));
     return BD_OK;
 }
 
 int bd_trainer_mean_loss(bd_trainer t, int32_t reset, float* mean_host) {
-    if (!t || !mean_host) return fail(BD_EINVAL, "bd_trainer_mean_loss: null argument");
-    BDT_HIP(hipSetDevice(t->device));
-    BDT_HIP(hipStreamSynchronize(t->last));
-    double acc[2] = {0.0, 0.0};
-    BDT_HIP(hipMemcpy(acc, t->acc, sizeof(acc), hipMemcpyDeviceToHost));
-    *mean_host = acc[1] > 0.0 ? (float)(acc[0] / acc[1]) : 0.0f;
-    if (reset) BDT_HIP(hipMemset(t->acc, 0, sizeof(acc)));
-    return BD_OK;
+    return bd::mean_losses(t, reset, mean_host, "bd_trainer_mean_loss");
 }
 
-int64_t bd_trainer_workspace_floats(bd_trainer t) {
-    if (!t) return fail(BD_EINVAL, "bd_trainer_workspace_floats: null handle");
-    return t->ws_floats;
-}
+int64_t bd_trainer_workspace_floats(bd_trainer t) { return bd::workspace_floats(t, "bd_trainer_workspace_floats"); }
 
-int bd_trainer_workspace_fill(bd_trainer t, uint32_t pattern) {
-    if (!t) return fail(BD_EINVAL, "bd_trainer_workspace_fill: null handle");
-    BDT_HIP(hipSetDevice(t->device));
-    BDT_HIP(hipStreamSynchronize(t->last));
-    hipLaunchKernelGGL(bd::fill_kernel, dim3(256), dim3(256), 0, t->last, reinterpret_cast<uint32_t*>(t->ws), (size_t)t->ws_floats,
-                       pattern);
-    BDT_HIP(hipGetLastError());
-    BDT_HIP(hipStreamSynchronize(t->last));
-    return BD_OK;
-}
+int bd_trainer_workspace_fill(bd_trainer t, uint32_t pattern) { return bd::workspace_fill(t, pattern, "bd_trainer_workspace_fill"); }
 
 int bd_trainer_workspace_read(bd_trainer t, float* host, int64_t floats) {
-    if (!t || !host || floats < 0 || floats > t->ws_floats) return fail(BD_EINVAL, "bd_trainer_workspace_read: bad argument");
-    BDT_HIP(hipSetDevice(t->device));
-    BDT_HIP(hipStreamSynchronize(t->last));
-    BDT_HIP(hipMemcpy(host, t->ws, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost));
-    return BD_OK;
+    return bd::workspace_read(t, host, floats, "bd_trainer_workspace_read");
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
-// Device routines of the classifier-head trainer, shared by headtrain.hip (one stack: include/buzzdetect_train.h) and
-// headbank.hip (a bank of one-layer heads: include/buzzdetect_bank.h).  Both files call these and nothing else for a product, a
-// row's loss, a partial's sum or an update, so a member of a bank and a trainer on its own run the same instructions in the same
-// order: the bit identity the bank promises rests on this file being the only copy.
+// Device routines of the classifier-head trainer, shared by headtrain.hip (one stack: include/buzzdetect_train.h),
+// headbank.hip (a bank of one-layer heads: include/buzzdetect_bank.h) and stackbank.hip (a bank of Dense stacks:
+// include/buzzdetect_stackbank.h).  The three files call these and nothing else for a product, a row's loss, a partial's sum
+// or an update, so a member of a bank and a trainer on its own run the same instructions in the same order: the bit identity
+// the banks promise rests on this file being the only copy.  (headtrain_host.h is its counterpart for the host side.)
 //
 // Every product is one routine, mma_chain: a wave owns a 32 x 32 output tile and walks the reduced index alone in ascending
 // super-steps of 8, in headmlp.hip's operand map (lane l supplies A[i = l & 31][k] and B[k][j = l & 31], lane-half h takes

@@ -1,6 +1,6 @@
 """Fit a classifier head on the GPU and save it as a model directory (include/buzzdetect_train.h, csrc/headtrain.hip;
 many heads at once: include/buzzdetect_bank.h, csrc/headbank.hip; many stacks at once: include/buzzdetect_stackbank.h,
-csrc/stackbank.hip).
+csrc/stackbank.hip; the host side the three share: csrc/headtrain_host.h, and ``_Handle`` here).
 
 The bring-your-own-labels loop without a foreign toolchain:
 
@@ -82,202 +82,54 @@ def glorot_layers(rng: np.random.Generator, widths: Sequence[int], activations: 
     return layers
 
 
-class Trainer:
-    """``bd_trainer_*`` on torch tensors: ``layers`` = [(kernel [in, out], bias [out], activation)] are the initial values."""
+class _Handle:
+    """What ``Trainer``, ``TrainerBank`` and ``TrainerStackBank`` share: the checks of loss, optimizer and device, the
+    ``bd_head_layer`` arrays, the checks of a batch, the current stream and the handle's end.  ``_prefix``: the C entry points
+    the methods call; ``_noun``: what the messages call the object."""
 
-    def __init__(self, layers, loss: str = "categorical", optimizer: str = "adam", learning_rate: float = 1e-3,
-                 beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, max_batch: int = 256,
-                 device: Optional[int] = None):
-        import torch
-        self._handle = C.c_void_p()
-        self._lib = _lib.load()
-        if loss not in _lib.TRAIN_LOSSES:
-            raise ValueError(f'loss must be one of {sorted(_lib.TRAIN_LOSSES)}, not "{loss}"')
-        if optimizer not in _lib.TRAIN_OPTIMIZERS:
-            raise ValueError(f'optimizer must be one of {sorted(_lib.TRAIN_OPTIMIZERS)}, not "{optimizer}"')
-        if not torch.cuda.is_available():
-            raise RuntimeError("buzzdetect_amd: no HIP device visible to PyTorch; the trainer has no CPU path")
-        self.device_index = torch.cuda.current_device() if device is None else int(device)
-        self.device = torch.device("cuda", self.device_index)
-        self.loss = loss
-        self.max_batch = int(max_batch)
-        self.shapes = [tuple(np.shape(k)) for k, _, _ in layers]
-        self.n_out = self.shapes[-1][1]
-        arr = (_lib.bd_head_layer * len(layers))()
-        keep = []
-        for i, (kernel, bias, activation) in enumerate(layers):
-            k = np.ascontiguousarray(kernel, dtype=np.float32)
-            b = np.ascontiguousarray(bias, dtype=np.float32)
-            keep += [k, b]
-            arr[i].kernel = k.ctypes.data_as(C.POINTER(C.c_float))
-            arr[i].bias = b.ctypes.data_as(C.POINTER(C.c_float))
-            arr[i].n_in, arr[i].n_out = k.shape
-            arr[i].activation = _lib.HEAD_ACTIVATIONS[activation]
-        opt = _lib.bd_train_optimizer(_lib.TRAIN_OPTIMIZERS[optimizer], learning_rate, beta_1, beta_2, epsilon, 0)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.bd_trainer_create(self.device_index, arr, len(layers), _lib.TRAIN_LOSSES[loss], C.byref(opt),
-                                                   self.max_batch, C.byref(self._handle)))
-            self._loss_word = torch.zeros(1, dtype=torch.float32, device=self.device)
-
-    def close(self) -> None:
-        if getattr(self, "_handle", None) is not None and self._handle.value:
-            self._lib.bd_trainer_destroy(self._handle)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _batch(self, X, rows, targets, B, weights=None):
-        import torch
-        if weights is not None and (weights.dtype != torch.float32 or not weights.is_contiguous() or weights.numel() < B
-                                    or weights.device != self.device):
-            raise ValueError("weights must be a contiguous float32 tensor of at least B entries on the trainer's device")
-        if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.device != self.device:
-            raise ValueError("X must be a float32 [N, >= 1024] matrix on the trainer's device with unit column stride")
-        if rows is not None and (rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() < B):
-            raise ValueError("rows must be a contiguous int32 tensor of at least B entries")
-        want = torch.float32 if self.loss == "binary" else torch.int32
-        if targets.dtype != want or not targets.is_contiguous() or targets.numel() < B * (self.n_out if self.loss == "binary" else 1):
-            raise ValueError(f"targets must be a contiguous {want} tensor covering the batch")
-        if rows is None and X.shape[0] < B:
-            raise ValueError("X has fewer than B rows")
-        return (C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(rows.data_ptr()) if rows is not None else None,
-                C.c_void_p(targets.data_ptr()), int(B), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-
-    def step(self, X, rows, targets, B: int, weights=None) -> None:
-        """One optimisation step on ``B`` rows: ``rows`` (int32, device) names them in ``X``, or None for the first ``B``;
-        ``targets`` are in batch order, and so are ``weights`` (float32, device: the rows' loss weights; None runs the
-        unweighted kernels).  Enqueued on the current stream."""
-        x, ldx, r, t, b, stream = self._batch(X, rows, targets, B, weights)
-        if weights is None:
-            _lib.check(self._lib.bd_trainer_step(self._handle, x, ldx, r, t, b, stream))
-        else:
-            _lib.check(self._lib.bd_trainer_step_weighted(self._handle, x, ldx, r, t, C.c_void_p(weights.data_ptr()), b, stream))
-
-    def loss_into(self, X, rows, targets, B: int, out, weights=None) -> None:
-        """Forward pass and mean (with ``weights``: weighted, still divided by ``B``) loss of the batch into the device float
-        ``out[0]`` (no synchronisation)."""
-        x, ldx, r, t, b, stream = self._batch(X, rows, targets, B, weights)
-        if weights is None:
-            _lib.check(self._lib.bd_trainer_loss(self._handle, x, ldx, r, t, b, C.c_void_p(out.data_ptr()), stream))
-        else:
-            _lib.check(self._lib.bd_trainer_loss_weighted(self._handle, x, ldx, r, t, C.c_void_p(weights.data_ptr()), b,
-                                                          C.c_void_p(out.data_ptr()), stream))
-
-    def loss_of(self, X, rows, targets, B: int, weights=None) -> float:
-        self.loss_into(X, rows, targets, B, self._loss_word, weights)
-        return float(self._loss_word.cpu()[0])
-
-    def set_weight_decay(self, weight_decay: float) -> None:
-        """Decoupled decay of the steps from now on: kernels (not biases) shrink by ``lr * weight_decay`` of themselves
-        before the optimizer's update.  0 switches it off."""
-        _lib.check(self._lib.bd_trainer_set_weight_decay(self._handle, float(weight_decay)))
-
-    def set_learning_rate(self, learning_rate: float) -> None:
-        """The learning rate of the steps from now on."""
-        _lib.check(self._lib.bd_trainer_set_learning_rate(self._handle, float(learning_rate)))
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def snapshot(self) -> None:
-        """Copy the parameters (not Adam's slots, not the step count) to the trainer's second buffer, on the current stream."""
-        _lib.check(self._lib.bd_trainer_snapshot(self._handle, self._stream()))
-
-    def restore(self) -> None:
-        """Copy the last ``snapshot`` back over the parameters, on the current stream; an error if there is none."""
-        _lib.check(self._lib.bd_trainer_restore(self._handle, self._stream()))
-
-    def _pair(self, fn, layer: int) -> Tuple[np.ndarray, np.ndarray]:
-        k, n = self.shapes[layer]
-        w, b = np.empty((k, n), dtype=np.float32), np.empty(n, dtype=np.float32)
-        _lib.check(fn(self._handle, layer, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
-        return w, b
-
-    def gradients(self, layer: int) -> Tuple[np.ndarray, np.ndarray]:
-        """(dW, db) of the last step."""
-        return self._pair(self._lib.bd_trainer_gradients, layer)
-
-    def read(self, layer: int) -> Tuple[np.ndarray, np.ndarray]:
-        """(kernel, bias) as they stand."""
-        return self._pair(self._lib.bd_trainer_read, layer)
-
-    def logits(self, B: int) -> np.ndarray:
-        """The logits of the last ``step`` / ``loss_*`` call's ``B`` rows."""
-        out = np.empty((B, self.n_out), dtype=np.float32)
-        _lib.check(self._lib.bd_trainer_logits(self._handle, B, out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def mean_loss(self, reset: bool = True) -> float:
-        """Mean training loss per row over the steps since the last reset (accumulated on the device)."""
-        v = C.c_float()
-        _lib.check(self._lib.bd_trainer_mean_loss(self._handle, 1 if reset else 0, C.byref(v)))
-        return float(v.value)
-
-    def set_fusion(self, fused: bool) -> None:
-        _lib.check(self._lib.bd_trainer_set_fusion(self._handle, 1 if fused else 0))
-
-    def workspace_fill(self, pattern: int) -> None:
-        _lib.check(self._lib.bd_trainer_workspace_fill(self._handle, pattern))
-
-    def workspace(self) -> np.ndarray:
-        out = np.empty(_lib.check(self._lib.bd_trainer_workspace_floats(self._handle)), dtype=np.float32)
-        _lib.check(self._lib.bd_trainer_workspace_read(self._handle, out.ctypes.data_as(C.c_void_p), out.size))
-        return out
-
-
-class TrainerBank:
-    """``bd_bank_*`` on torch tensors (include/buzzdetect_bank.h): ``members`` = [(kernel [1024, C], bias [C]), ...] are the
-    initial values of M one-layer heads that share every step's rows, targets and batch order and keep their own parameters,
-    slots, rate, decay, row weights, running loss, snapshot and frozen flag.  Member m is, bit for bit, the ``Trainer`` that
-    got the same calls with row m of the weights."""
-
-    _prefix = "bd_bank_"                # the C entry points the methods call: TrainerStackBank has the same ones under its own
+    _prefix = "bd_trainer_"
+    _noun = "trainer"
 
     def _call(self, name, *args):
         return _lib.check(getattr(self._lib, self._prefix + name)(self._handle, *args))
 
-    def __init__(self, members, loss: str = "categorical", optimizer: str = "adam", learning_rate: float = 1e-3,
-                 beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, max_batch: int = 256,
-                 device: Optional[int] = None):
-        import torch
+    def _begin(self, loss: str, optimizer: str) -> None:
         self._handle = C.c_void_p()
         self._lib = _lib.load()
         if loss not in _lib.TRAIN_LOSSES:
             raise ValueError(f'loss must be one of {sorted(_lib.TRAIN_LOSSES)}, not "{loss}"')
         if optimizer not in _lib.TRAIN_OPTIMIZERS:
             raise ValueError(f'optimizer must be one of {sorted(_lib.TRAIN_OPTIMIZERS)}, not "{optimizer}"')
-        members = list(members)
-        if not members:
-            raise ValueError("a bank needs at least one member")
+
+    def _on_device(self, loss: str, max_batch: int, device: Optional[int]) -> None:
+        import torch
         if not torch.cuda.is_available():
             raise RuntimeError("buzzdetect_amd: no HIP device visible to PyTorch; the trainer has no CPU path")
         self.device_index = torch.cuda.current_device() if device is None else int(device)
         self.device = torch.device("cuda", self.device_index)
         self.loss = loss
         self.max_batch = int(max_batch)
-        self.n_members = len(members)
-        arr = (_lib.bd_head_layer * len(members))()
-        keep = []
-        for i, member in enumerate(members):
-            k = np.ascontiguousarray(member[0], dtype=np.float32)
-            b = np.ascontiguousarray(member[1], dtype=np.float32)
-            if k.ndim != 2 or b.shape != (k.shape[1],):
-                raise ValueError(f"member {i}: a kernel [1024, C] and a bias [C], not {k.shape} and {b.shape}")
-            keep += [k, b]
-            arr[i].kernel = k.ctypes.data_as(C.POINTER(C.c_float))
-            arr[i].bias = b.ctypes.data_as(C.POINTER(C.c_float))
-            arr[i].n_in, arr[i].n_out = k.shape
-            arr[i].activation = _lib.HEAD_ACTIVATIONS["linear"]
-        self.n_out = int(arr[0].n_out)
+
+    @staticmethod
+    def _fill_layer(at, kernel, bias, activation, keep, what=None) -> None:
+        """One ``bd_head_layer`` from (kernel, bias, activation); the float32 arrays it points to go to ``keep``.  ``what``
+        (who and which shapes, for the message) asks for the shapes to be checked."""
+        k = np.ascontiguousarray(kernel, dtype=np.float32)
+        b = np.ascontiguousarray(bias, dtype=np.float32)
+        if what is not None and (k.ndim != 2 or b.shape != (k.shape[1],)):
+            raise ValueError(f"{what}, not {k.shape} and {b.shape}")
+        keep += [k, b]
+        at.kernel = k.ctypes.data_as(C.POINTER(C.c_float))
+        at.bias = b.ctypes.data_as(C.POINTER(C.c_float))
+        at.n_in, at.n_out = k.shape
+        at.activation = _lib.HEAD_ACTIVATIONS[activation]
+
+    def _create(self, arr, counts, optimizer, learning_rate, beta_1, beta_2, epsilon) -> None:
+        import torch
         opt = _lib.bd_train_optimizer(_lib.TRAIN_OPTIMIZERS[optimizer], learning_rate, beta_1, beta_2, epsilon, 0)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.bd_bank_create(self.device_index, arr, len(members), _lib.TRAIN_LOSSES[loss], C.byref(opt),
-                                                self.max_batch, C.byref(self._handle)))
+            _lib.check(getattr(self._lib, self._prefix + "create")(self.device_index, arr, *counts, _lib.TRAIN_LOSSES[self.loss],
+                                                                  C.byref(opt), self.max_batch, C.byref(self._handle)))
 
     def close(self) -> None:
         if getattr(self, "_handle", None) is not None and self._handle.value:
@@ -294,10 +146,11 @@ class TrainerBank:
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _batch(self, X, rows, targets, B, weights=None):
+    def _check_batch(self, X, rows, targets, B):
+        """(X, ldx, rows, targets) as the C calls take them; ``targets`` may be None where the call has none."""
         import torch
         if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.device != self.device:
-            raise ValueError("X must be a float32 [N, >= 1024] matrix on the bank's device with unit column stride")
+            raise ValueError(f"X must be a float32 [N, >= 1024] matrix on the {self._noun}'s device with unit column stride")
         if rows is not None and (rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() < B):
             raise ValueError("rows must be a contiguous int32 tensor of at least B entries")
         if rows is None and X.shape[0] < B:
@@ -306,14 +159,149 @@ class TrainerBank:
             want = torch.float32 if self.loss == "binary" else torch.int32
             if targets.dtype != want or not targets.is_contiguous() or targets.numel() < B * (self.n_out if self.loss == "binary" else 1):
                 raise ValueError(f"targets must be a contiguous {want} tensor covering the batch")
+        return (C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(rows.data_ptr()) if rows is not None else None,
+                C.c_void_p(targets.data_ptr()) if targets is not None else None)
+
+    def workspace_fill(self, pattern: int) -> None:
+        self._call("workspace_fill", pattern)
+
+    def workspace(self) -> np.ndarray:
+        out = np.empty(self._call("workspace_floats"), dtype=np.float32)
+        self._call("workspace_read", out.ctypes.data_as(C.c_void_p), out.size)
+        return out
+
+
+class Trainer(_Handle):
+    """``bd_trainer_*`` on torch tensors: ``layers`` = [(kernel [in, out], bias [out], activation)] are the initial values."""
+
+    def __init__(self, layers, loss: str = "categorical", optimizer: str = "adam", learning_rate: float = 1e-3,
+                 beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, max_batch: int = 256,
+                 device: Optional[int] = None):
+        import torch
+        self._begin(loss, optimizer)
+        self._on_device(loss, max_batch, device)
+        self.shapes = [tuple(np.shape(k)) for k, _, _ in layers]
+        self.n_out = self.shapes[-1][1]
+        arr = (_lib.bd_head_layer * len(layers))()
+        keep = []
+        for i, (kernel, bias, activation) in enumerate(layers):
+            self._fill_layer(arr[i], kernel, bias, activation, keep)
+        self._create(arr, (len(layers),), optimizer, learning_rate, beta_1, beta_2, epsilon)
+        with torch.cuda.device(self.device):
+            self._loss_word = torch.zeros(1, dtype=torch.float32, device=self.device)
+
+    def _batch(self, X, rows, targets, B, weights=None):
+        import torch
+        if weights is not None and (weights.dtype != torch.float32 or not weights.is_contiguous() or weights.numel() < B
+                                    or weights.device != self.device):
+            raise ValueError("weights must be a contiguous float32 tensor of at least B entries on the trainer's device")
+        return self._check_batch(X, rows, targets, B) + (int(B), self._stream())
+
+    def step(self, X, rows, targets, B: int, weights=None) -> None:
+        """One optimisation step on ``B`` rows: ``rows`` (int32, device) names them in ``X``, or None for the first ``B``;
+        ``targets`` are in batch order, and so are ``weights`` (float32, device: the rows' loss weights; None runs the
+        unweighted kernels).  Enqueued on the current stream."""
+        x, ldx, r, t, b, stream = self._batch(X, rows, targets, B, weights)
+        if weights is None:
+            self._call("step", x, ldx, r, t, b, stream)
+        else:
+            self._call("step_weighted", x, ldx, r, t, C.c_void_p(weights.data_ptr()), b, stream)
+
+    def loss_into(self, X, rows, targets, B: int, out, weights=None) -> None:
+        """Forward pass and mean (with ``weights``: weighted, still divided by ``B``) loss of the batch into the device float
+        ``out[0]`` (no synchronisation)."""
+        x, ldx, r, t, b, stream = self._batch(X, rows, targets, B, weights)
+        if weights is None:
+            self._call("loss", x, ldx, r, t, b, C.c_void_p(out.data_ptr()), stream)
+        else:
+            self._call("loss_weighted", x, ldx, r, t, C.c_void_p(weights.data_ptr()), b, C.c_void_p(out.data_ptr()), stream)
+
+    def loss_of(self, X, rows, targets, B: int, weights=None) -> float:
+        self.loss_into(X, rows, targets, B, self._loss_word, weights)
+        return float(self._loss_word.cpu()[0])
+
+    def set_weight_decay(self, weight_decay: float) -> None:
+        """Decoupled decay of the steps from now on: kernels (not biases) shrink by ``lr * weight_decay`` of themselves
+        before the optimizer's update.  0 switches it off."""
+        self._call("set_weight_decay", float(weight_decay))
+
+    def set_learning_rate(self, learning_rate: float) -> None:
+        """The learning rate of the steps from now on."""
+        self._call("set_learning_rate", float(learning_rate))
+
+    def snapshot(self) -> None:
+        """Copy the parameters (not Adam's slots, not the step count) to the trainer's second buffer, on the current stream."""
+        self._call("snapshot", self._stream())
+
+    def restore(self) -> None:
+        """Copy the last ``snapshot`` back over the parameters, on the current stream; an error if there is none."""
+        self._call("restore", self._stream())
+
+    def _pair(self, name, layer: int) -> Tuple[np.ndarray, np.ndarray]:
+        k, n = self.shapes[layer]
+        w, b = np.empty((k, n), dtype=np.float32), np.empty(n, dtype=np.float32)
+        self._call(name, layer, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p))
+        return w, b
+
+    def gradients(self, layer: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(dW, db) of the last step."""
+        return self._pair("gradients", layer)
+
+    def read(self, layer: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(kernel, bias) as they stand."""
+        return self._pair("read", layer)
+
+    def logits(self, B: int) -> np.ndarray:
+        """The logits of the last ``step`` / ``loss_*`` call's ``B`` rows."""
+        out = np.empty((B, self.n_out), dtype=np.float32)
+        self._call("logits", B, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def mean_loss(self, reset: bool = True) -> float:
+        """Mean training loss per row over the steps since the last reset (accumulated on the device)."""
+        v = C.c_float()
+        self._call("mean_loss", 1 if reset else 0, C.byref(v))
+        return float(v.value)
+
+    def set_fusion(self, fused: bool) -> None:
+        self._call("set_fusion", 1 if fused else 0)
+
+
+class TrainerBank(_Handle):
+    """``bd_bank_*`` on torch tensors (include/buzzdetect_bank.h): ``members`` = [(kernel [1024, C], bias [C]), ...] are the
+    initial values of M one-layer heads that share every step's rows, targets and batch order and keep their own parameters,
+    slots, rate, decay, row weights, running loss, snapshot and frozen flag.  Member m is, bit for bit, the ``Trainer`` that
+    got the same calls with row m of the weights."""
+
+    _prefix = "bd_bank_"                # TrainerStackBank has the same entry points under its own
+    _noun = "bank"
+
+    def __init__(self, members, loss: str = "categorical", optimizer: str = "adam", learning_rate: float = 1e-3,
+                 beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, max_batch: int = 256,
+                 device: Optional[int] = None):
+        self._begin(loss, optimizer)
+        members = list(members)
+        if not members:
+            raise ValueError("a bank needs at least one member")
+        self._on_device(loss, max_batch, device)
+        self.n_members = len(members)
+        arr = (_lib.bd_head_layer * len(members))()
+        keep = []
+        for i, member in enumerate(members):
+            self._fill_layer(arr[i], member[0], member[1], "linear", keep, f"member {i}: a kernel [1024, C] and a bias [C]")
+        self.n_out = int(arr[0].n_out)
+        self._create(arr, (len(members),), optimizer, learning_rate, beta_1, beta_2, epsilon)
+
+    def _batch(self, X, rows, targets, B, weights=None):
+        import torch
+        x, ldx, r, t = self._check_batch(X, rows, targets, B)
         w, ldw = None, 0
         if weights is not None:
             if weights.dtype != torch.float32 or weights.dim() != 2 or weights.shape[0] != self.n_members or weights.shape[1] < B \
                     or weights.stride(1) != 1 or weights.device != self.device or (self.n_members > 1 and weights.stride(0) < B):
                 raise ValueError("weights must be a float32 [members, >= B] matrix on the bank's device with unit column stride")
             w, ldw = C.c_void_p(weights.data_ptr()), max(int(weights.stride(0)), int(B))
-        return (C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(rows.data_ptr()) if rows is not None else None,
-                C.c_void_p(targets.data_ptr()) if targets is not None else None, w, ldw, int(B))
+        return x, ldx, r, t, w, ldw, int(B)
 
     def step(self, X, rows, targets, B: int, weights=None) -> None:
         """One optimisation step of every member that is not frozen on ``B`` rows (``rows``, ``targets`` as ``Trainer.step``
@@ -381,14 +369,6 @@ class TrainerBank:
         self._call("mean_loss", 1 if reset else 0, out.ctypes.data_as(C.c_void_p))
         return out
 
-    def workspace_fill(self, pattern: int) -> None:
-        self._call("workspace_fill", pattern)
-
-    def workspace(self) -> np.ndarray:
-        out = np.empty(self._call("workspace_floats"), dtype=np.float32)
-        self._call("workspace_read", out.ctypes.data_as(C.c_void_p), out.size)
-        return out
-
 
 class TrainerStackBank(TrainerBank):
     """``bd_stackbank_*`` on torch tensors (include/buzzdetect_stackbank.h): ``members`` = [[(kernel, bias, activation), ...],
@@ -401,23 +381,12 @@ class TrainerStackBank(TrainerBank):
     def __init__(self, members, loss: str = "categorical", optimizer: str = "adam", learning_rate: float = 1e-3,
                  beta_1: float = 0.9, beta_2: float = 0.999, epsilon: float = 1e-7, max_batch: int = 256,
                  device: Optional[int] = None):
-        import torch
-        self._handle = C.c_void_p()
-        self._lib = _lib.load()
-        if loss not in _lib.TRAIN_LOSSES:
-            raise ValueError(f'loss must be one of {sorted(_lib.TRAIN_LOSSES)}, not "{loss}"')
-        if optimizer not in _lib.TRAIN_OPTIMIZERS:
-            raise ValueError(f'optimizer must be one of {sorted(_lib.TRAIN_OPTIMIZERS)}, not "{optimizer}"')
+        self._begin(loss, optimizer)
         members = [list(member) for member in members]
         if not members or not members[0]:
             raise ValueError("a bank needs at least one member of at least one layer")
         n_layers = len(members[0])
-        if not torch.cuda.is_available():
-            raise RuntimeError("buzzdetect_amd: no HIP device visible to PyTorch; the trainer has no CPU path")
-        self.device_index = torch.cuda.current_device() if device is None else int(device)
-        self.device = torch.device("cuda", self.device_index)
-        self.loss = loss
-        self.max_batch = int(max_batch)
+        self._on_device(loss, max_batch, device)
         self.n_members = len(members)
         arr = (_lib.bd_head_layer * (len(members) * n_layers))()
         keep = []
@@ -425,22 +394,11 @@ class TrainerStackBank(TrainerBank):
             if len(member) != n_layers:
                 raise ValueError(f"member {i} has {len(member)} layers, member 0 has {n_layers}")
             for l, (kernel, bias, activation) in enumerate(member):
-                k = np.ascontiguousarray(kernel, dtype=np.float32)
-                b = np.ascontiguousarray(bias, dtype=np.float32)
-                if k.ndim != 2 or b.shape != (k.shape[1],):
-                    raise ValueError(f"member {i}, layer {l}: a kernel [in, out] and a bias [out], not {k.shape} and {b.shape}")
-                keep += [k, b]
-                at = arr[i * n_layers + l]
-                at.kernel = k.ctypes.data_as(C.POINTER(C.c_float))
-                at.bias = b.ctypes.data_as(C.POINTER(C.c_float))
-                at.n_in, at.n_out = k.shape
-                at.activation = _lib.HEAD_ACTIVATIONS[activation]
+                self._fill_layer(arr[i * n_layers + l], kernel, bias, activation, keep,
+                                 f"member {i}, layer {l}: a kernel [in, out] and a bias [out]")
         self.shapes = [(int(arr[l].n_in), int(arr[l].n_out)) for l in range(n_layers)]
         self.n_out = self.shapes[-1][1]
-        opt = _lib.bd_train_optimizer(_lib.TRAIN_OPTIMIZERS[optimizer], learning_rate, beta_1, beta_2, epsilon, 0)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.bd_stackbank_create(self.device_index, arr, len(members), n_layers, _lib.TRAIN_LOSSES[loss],
-                                                     C.byref(opt), self.max_batch, C.byref(self._handle)))
+        self._create(arr, (len(members), n_layers), optimizer, learning_rate, beta_1, beta_2, epsilon)
 
     def _pair(self, name, member: int, layer: int) -> Tuple[np.ndarray, np.ndarray]:
         if not 0 <= int(layer) < len(self.shapes):

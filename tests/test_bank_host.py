@@ -43,6 +43,8 @@ def test_the_trainer_and_the_bank_share_one_header_of_device_routines():
             assert not re.search(r"__device__[^;{]*\b" + name + r"\(", text), f"{source} defines {name}"
     for source in ("headtrain.hip", "headbank.hip"):
         assert '#include "headtrain_device.h"' in open(os.path.join(build.CSRC, source)).read()
+        assert '#include "headtrain_host.h"' in open(os.path.join(build.CSRC, source)).read()      # and one host side
+    assert "__device__" not in open(os.path.join(build.CSRC, "headtrain_host.h")).read()
 
 
 def test_every_bank_call_refuses_null_before_anything_is_enqueued():
