@@ -347,6 +347,29 @@ MIX_PROTOTYPES = {
                               C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
+SEARCH_ABI_VERSION = 1
+SEARCH_DIM = 1024
+SEARCH_MAX_QUERIES = 1024
+SEARCH_MAX_K = 1024
+SEARCH_MAX_WINDOWS = 1 << 20
+SEARCH_NORM_FLOOR = 1e-30
+SEARCH_METRICS = {"dot": 0, "cosine": 1}
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_search.h
+SEARCH_PROTOTYPES = {
+    "bd_search_abi_version": (C.c_int, []),
+    "bd_search_packed_floats": (C.c_int64, [C.c_int32]),
+    "bd_search_pack_queries": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_search_norms": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bd_search_norms_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_search_scores": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_int64, C.c_void_p]),
+    "bd_search_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                   C.c_void_p]),
+    "bd_search_update_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32]),
+    "bd_search_decode_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -380,7 +403,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     lib = C.CDLL(path)
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
             + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ENSEMBLE_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
-            + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()):
+            + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
+            + list(SEARCH_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -406,6 +430,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: stack-bank ABI version {lib.bd_stackbank_abi_version()} != {STACKBANK_ABI_VERSION}; rebuild")
     if lib.bd_mix_abi_version() != MIX_ABI_VERSION:
         raise RuntimeError(f"{path}: mixer ABI version {lib.bd_mix_abi_version()} != {MIX_ABI_VERSION}; rebuild")
+    if lib.bd_search_abi_version() != SEARCH_ABI_VERSION:
+        raise RuntimeError(f"{path}: search ABI version {lib.bd_search_abi_version()} != {SEARCH_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 
