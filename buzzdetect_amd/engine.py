@@ -514,6 +514,10 @@ class HipEngine:
             self._workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
         return self._workspace
 
+    def _empty(self, shape) -> torch.Tensor:
+        """The float32 device tensor a result is written into (a seam for tests that hand out guarded memory)."""
+        return torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
+
     def to_device(self, samples) -> torch.Tensor:
         """1-D float32 chunk (numpy / torch CPU / torch device) -> contiguous device tensor."""
         if isinstance(samples, DeviceResult):
@@ -715,11 +719,11 @@ class HipEngine:
         with self._lock, torch.cuda.device(self.device):
             ws_bytes = _lib.check(self._lib.bd_batch_workspace_bytes(self._handle, lengths, nc, hop, step))
             ws = self._ws(ws_bytes)
-            emb = torch.empty((total, _lib.EMBEDDING_SIZE), dtype=torch.float32, device=self.device) if want_embeddings else None
+            emb = self._empty((total, _lib.EMBEDDING_SIZE)) if want_embeddings else None
             logits = None
             if want_logits:
                 if out is None:
-                    logits = torch.empty((total, self.n_classes), dtype=torch.float32, device=self.device)
+                    logits = self._empty((total, self.n_classes))
                 else:       # caller-owned rows (e.g. a slice of a per-recording buffer that is gathered later)
                     if (tuple(out.shape) != (total, self.n_classes) or out.dtype != torch.float32 or
                             out.device != self.device or not out.is_contiguous() or out.data_ptr() % 16):
@@ -802,7 +806,7 @@ class HipEngine:
         x = self.to_device(samples)
         h, w, c = C.c_int32(), C.c_int32(), C.c_int32()
         _lib.check(self._lib.bd_stage_shape(stage, C.byref(h), C.byref(w), C.byref(c)))
-        out = torch.empty((windows, h.value, w.value, c.value), dtype=torch.float32, device=self.device)
+        out = self._empty((windows, h.value, w.value, c.value))
         with self._lock, torch.cuda.device(self.device):
             ws_bytes = _lib.check(self._lib.bd_workspace_bytes(self._handle, x.numel(), hop, step))
             ws = self._ws(ws_bytes)
