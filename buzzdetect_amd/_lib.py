@@ -370,6 +370,31 @@ SEARCH_PROTOTYPES = {
     "bd_search_decode_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
+CLUSTER_ABI_VERSION = 1
+CLUSTER_DIM = 1024
+CLUSTER_MAX_CLUSTERS = 1024
+CLUSTER_MAX_ROWS = 1 << 24
+CLUSTER_CHUNK = 256
+CLUSTER_STAT_SLICE = 256
+CLUSTER_ORDER_SLICE = 1024
+CLUSTER_METRICS = {"euclidean": 0, "cosine": 1}
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_cluster.h
+CLUSTER_PROTOTYPES = {
+    "bd_cluster_abi_version": (C.c_int, []),
+    "bd_cluster_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "bd_cluster_assign": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "bd_cluster_order": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_cluster_order_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_cluster_centroids": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_cluster_centroids_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_cluster_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_cluster_stats_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -404,7 +429,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
             + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ENSEMBLE_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
-            + list(SEARCH_PROTOTYPES.items()):
+            + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -432,6 +457,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: mixer ABI version {lib.bd_mix_abi_version()} != {MIX_ABI_VERSION}; rebuild")
     if lib.bd_search_abi_version() != SEARCH_ABI_VERSION:
         raise RuntimeError(f"{path}: search ABI version {lib.bd_search_abi_version()} != {SEARCH_ABI_VERSION}; rebuild")
+    if lib.bd_cluster_abi_version() != CLUSTER_ABI_VERSION:
+        raise RuntimeError(f"{path}: cluster ABI version {lib.bd_cluster_abi_version()} != {CLUSTER_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 
