@@ -57,16 +57,14 @@ __host__ __device__ __forceinline__ float ar_pcm(short v) { return (float)v * (1
 __host__ __device__ __forceinline__ float ar_mono(const float* __restrict__ in, long long i, int channels) {
     if (channels == 1) return in[i];
     if (channels == 2) return (in[2 * i] + in[2 * i + 1]) * 0.5f;
-    float m = 0.0f;
-    for (int ch = 0; ch < channels; ++ch) m += in[i * channels + ch];
-    return m / (float)channels;
+    const float* __restrict__ frame = in + i * channels;
+    return np_row_sum(channels, [&](int ch) { return frame[ch]; }) / (float)channels;
 }
 __host__ __device__ __forceinline__ float ar_mono(const short* __restrict__ in, long long i, int channels) {
     if (channels == 1) return ar_pcm(in[i]);
     if (channels == 2) return (float)((int)in[2 * i] + (int)in[2 * i + 1]) * (1.0f / 65536.0f);      // exact
-    float m = 0.0f;
-    for (int ch = 0; ch < channels; ++ch) m += ar_pcm(in[i * channels + ch]);
-    return m / (float)channels;
+    const short* __restrict__ frame = in + i * channels;
+    return np_row_sum(channels, [&](int ch) { return ar_pcm(frame[ch]); }) / (float)channels;
 }
 
 // Row and Lagrange weights of an output whose position is n + r / up input samples (interpolated tables): the phase

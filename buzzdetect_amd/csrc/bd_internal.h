@@ -128,6 +128,36 @@ bool fir_plan_build(int up, int down, const double* taps, int half, FirPlanHost*
 void launch_fir_mfma(const void* in, bool s16, int64_t n_in, int channels, const FirPlan& plan, float* out, int64_t n_out,
                      hipStream_t stream);
 
+// The sum of a frame's `n` channel values at(0) .. at(n - 1) in the order np.mean(axis=1) adds a float32 row (the
+// reference's downmix, src/stream/worker.py:116): below eight values one running sum; from eight on eight running sums
+// over blocks of eight, folded as a tree, then the last n % 8 values in order.  Every resampler kernel and the any-ratio host
+// restatement divide this sum by n: the mean has the reference's bits.  (A row of more than 128 values NumPy first splits
+// in halves; that is not restated - such a row is still summed, in this order.)  Named sums, not an array: nothing here is
+// indexed at run time.
+template <typename F>
+__host__ __device__ __forceinline__ float np_row_sum(int n, F&& at) {
+    if (n < 8) {
+        float s = 0.0f;
+        for (int i = 0; i < n; ++i) s += at(i);
+        return s;
+    }
+    float r0 = at(0), r1 = at(1), r2 = at(2), r3 = at(3), r4 = at(4), r5 = at(5), r6 = at(6), r7 = at(7);
+    int i = 8;
+    for (; i + 8 <= n; i += 8) {
+        r0 += at(i);
+        r1 += at(i + 1);
+        r2 += at(i + 2);
+        r3 += at(i + 3);
+        r4 += at(i + 4);
+        r5 += at(i + 5);
+        r6 += at(i + 6);
+        r7 += at(i + 7);
+    }
+    float s = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+    for (; i < n; ++i) s += at(i);
+    return 0.0f + s;                   // NumPy adds the row's sum to its initial 0: a frame of -0.0 gives +0.0
+}
+
 // The any-ratio resampler (anyrate.hip, include/buzzdetect_anyrate.h): geometry of one rate ratio.  The table is
 // [rows][kw] float32: row r holds g(q - W - phase_r), q = 0 .. 2 W, zero-padded to kw.
 struct AnyratePlan {

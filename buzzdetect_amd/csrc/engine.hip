@@ -764,7 +764,7 @@ static int resample_any(bd_handle h, const void* in_dev, bool s16, int64_t n_in,
             t.down = down;
             t.quality = quality;
             const std::vector<double> hd = design_taps(up, down, quality, &t.half);
-            // rounds 1-3's filter keeps its kernels (decimate_kernel / resample_kernel: bit for bit what it was); the long
+            // rounds 1-3's filter keeps its kernels (decimate_kernel / resample_kernel); the long
             // filter runs on the matrix cores where the ratio fits
             t.has_plan = quality == BD_RESAMPLE_HQ && bd::fir_plan_build(up, down, hd.data(), t.half, &t.fir);
             if (!t.has_plan && !(up == 1 && (down == 2 || down == 3) && t.half == 10 * down) &&

@@ -467,7 +467,7 @@ __global__ __launch_bounds__(256) void patches_kernel(const float* __restrict__ 
 // as one device pass).  y[j] = sum_i mono[i] * h[j*down - i*up + half], h = Kaiser(5.0)-windowed sinc of
 // 2*half + 1 taps scaled by `up` (the scipy.signal.resample_poly design; the reference's soxr_hq is a
 // different low-pass, so this stage is "parity unpinned" against the reference and pinned against its own
-// CPU restatement).  Taps are walked in increasing input index.
+// CPU restatement).  Taps are walked in increasing input index (resample_kernel: into eight interleaved sums).
 //
 // resample_kernel: a workgroup owns a tile of consecutive outputs.  It stages the channel mean of the input span
 // the tile needs (coalesced, converted once) and the filter in LDS, then every thread walks its outputs' taps out
@@ -492,9 +492,8 @@ template <typename T>
 __device__ __forceinline__ float mono_at(const T* __restrict__ in, long long i, int channels) {
     if (channels == 1) return pcm_to_float(in[i]);
     if (channels == 2) return stereo_mean(in, i);
-    float m = 0.0f;
-    for (int ch = 0; ch < channels; ++ch) m += pcm_to_float(in[i * channels + ch]);
-    return m / (float)channels;
+    const T* __restrict__ frame = in + i * channels;
+    return np_row_sum(channels, [&](int ch) { return pcm_to_float(frame[ch]); }) / (float)channels;
 }
 
 constexpr int kRsThreads = 256;
@@ -535,9 +534,10 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const T* __restric
         int t = (int)(c - ia * up + half);                  // tap of the first input sample; steps down by `up`
         int k = (int)(ia - i_lo);
         const int ke = (int)(ib - i_lo);
-        float acc = 0.0f;
-        // eight taps' operands are requested together, then accumulated in input order: the same sum as a one-tap loop
-        // (one LDS round trip per eight taps instead of per tap)
+        // eight taps' operands are requested together (one LDS round trip per eight taps instead of per tap) and go to eight
+        // running sums, tap e of every group to sum e, folded as a tree at the end: one float32 chain over the 2267 taps of
+        // 192 -> 16 kHz strayed up to 2.7e-6 from the float64 oracle on full-scale 16-bit PCM, eight chains stay below 4e-7
+        float sum[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         for (; k + 7 <= ke; k += 8, t -= 8 * up) {
             float x[8], w[8];
 #pragma unroll
@@ -546,8 +546,9 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const T* __restric
                 w[e] = TAPS_IN_LDS ? s_h[t - e * up] : h[t - e * up];
             }
 #pragma unroll
-            for (int e = 0; e < 8; ++e) acc = fmaf(x[e], w[e], acc);
+            for (int e = 0; e < 8; ++e) sum[e] = fmaf(x[e], w[e], sum[e]);
         }
+        float acc = ((sum[0] + sum[1]) + (sum[2] + sum[3])) + ((sum[4] + sum[5]) + (sum[6] + sum[7]));
         for (; k <= ke; ++k, t -= up) acc = fmaf(s_x[k], TAPS_IN_LDS ? s_h[t] : h[t], acc);
         out[j] = acc;
     }

@@ -116,25 +116,26 @@ __device__ __forceinline__ void fir_convert(const FirRaw<T, CH>& raw, float (&v)
     }
 }
 
-// the signal's edges (samples outside it are zero) and inputs of three or more channels: one sample at a time
-template <typename T>
+// the signal's edges (samples outside it are zero) and inputs of three or more channels: one sample at a time.  CH is the
+// kernel's: the mono and stereo kernels carry no code for other channel counts beside their filter and accumulators
+template <typename T, int CH>
 __device__ __forceinline__ void fir_slow8(const T* __restrict__ in, long long i0, long long n_in, int channels, float (&v)[8]) {
 #pragma unroll 1
     for (int e = 0; e < 8; ++e) {
         const long long i = i0 + e;
         float m = 0.0f;
         if (i >= 0 && i < n_in) {
-            if (channels == 1) {
+            if constexpr (CH == 1) {
                 m = FirIn<T>::one(in[i]);
-            } else if (channels == 2) {
+            } else if constexpr (CH == 2) {
                 if constexpr (sizeof(T) == 2) m = (float)((int)in[2 * i] + (int)in[2 * i + 1]) * 0.5f;
                 else m = FirIn<float>::one((in[2 * i] + in[2 * i + 1]) * 0.5f);
             } else {
-                float s = 0.0f;
-                for (int ch = 0; ch < channels; ++ch) {
-                    if constexpr (sizeof(T) == 2) s += (float)in[i * channels + ch] * (1.0f / 32768.0f);
-                    else s += in[i * channels + ch];
-                }
+                const T* __restrict__ frame = in + i * channels;
+                float s = np_row_sum(channels, [&](int ch) {
+                    if constexpr (sizeof(T) == 2) return (float)frame[ch] * (1.0f / 32768.0f);
+                    else return frame[ch];
+                });
                 s /= (float)channels;
                 if constexpr (sizeof(T) == 2) m = s * 32768.0f;
                 else m = FirIn<float>::one(s);
@@ -221,7 +222,7 @@ struct FirPrefetch {
                 if (fast >> it & 1u) {
                     if constexpr (CH != 0) fir_convert<T, (CH ? CH : 1)>(raw[it], v);
                 } else {
-                    fir_slow8(in, i0, n_in, channels, v);
+                    fir_slow8<T, CH>(in, i0, n_in, channels, v);
                 }
                 fir_put8(a_hi, a_lo, phys, v);
             }
@@ -262,7 +263,7 @@ struct FirPrefetch {
                 for (int gi = 0; gi < GROUP; ++gi) {
                     if (q0 + gi * kFirThreads >= total) break;
                     float v[8];
-                    fir_slow8(in, i0[gi], n_in, channels, v);
+                    fir_slow8<T, CH>(in, i0[gi], n_in, channels, v);
                     fir_put8(a_hi, a_lo, phys[gi], v);
                 }
             }

@@ -37,11 +37,11 @@ def same_bits(a, b):
 
 @pytest.mark.parametrize("rate_in", RATES + [-47999])
 def test_kernel_equals_host_restatement_bit_for_bit(engine, rate_in):
-    """Every rate bd_resample refuses (and 16 000 -> 47 999 Hz, listed as -47999) x {s16, f32} x {1, 2} channels."""
+    """Every rate bd_resample refuses (and 16 000 -> 47 999 Hz, listed as -47999) x {s16, f32} x {1, 2, 3, 6} channels."""
     rate_in, rate_out = (rate_in, 16000) if rate_in > 0 else (16000, -rate_in)
     rng = np.random.default_rng(rate_in)
     n = int(0.05 * rate_in) + 301 if rate_in < 10 ** 7 else 2 * 4099 * 170     # the last: 340 outputs of 774 k taps each
-    for channels in (1, 2):
+    for channels in (1, 2, 3, 6):
         x = rng.uniform(-1.0, 1.0, (n, channels)).astype(np.float32)
         q = np.floor(x * 32768.0).astype(np.int16)
         if channels == 1:

@@ -154,7 +154,8 @@ def test_read_flac_is_soundfile_float32(engine, tmp_path):
     np.testing.assert_array_equal(got, (pcm16 / 32768.0).astype(np.float32))
 
 
-FORMATS = [(16000, 1, 16, 4096, 7.3), (48000, 2, 16, 4608, 5.1), (44100, 1, 24, 4096, 6.7)]
+FORMATS = [(16000, 1, 16, 4096, 7.3), (48000, 2, 16, 4608, 5.1), (44100, 1, 24, 4096, 6.7), (48000, 6, 16, 4096, 5.1),
+           (44100, 3, 24, 4096, 6.7)]
 
 
 @pytest.mark.parametrize("fmt", range(len(FORMATS)))

@@ -118,14 +118,14 @@ RESAMPLE_CASES = [("hq", 48000), ("hq", 44100), ("hq", 192000), ("scipy", 48000)
 RESAMPLE_LENGTHS = (1, 7, 61, 5374, 4096 * 3 + 1)           # tests/test_resample.py's test_integer_decimation_edges, the short ones
 
 
-@pytest.mark.parametrize("channels", [1, 2])
+@pytest.mark.parametrize("channels", [1, 2, 3, 8])
 @pytest.mark.parametrize("engine_q,rate_in", RESAMPLE_CASES, indirect=["engine_q"])
 def test_resample_reads_zeros_behind_the_last_frame(engine_q, rate_in, channels):
     lib = engine_q._lib
     hold_resampler(engine_q, lib.bd_resample, lib.bd_resample_s16, rate_in, channels, RESAMPLE_LENGTHS)
 
 
-@pytest.mark.parametrize("channels", [1, 2])
+@pytest.mark.parametrize("channels", [1, 2, 3, 8])
 @pytest.mark.parametrize("rate_in", [47999, 768000])
 def test_resample_any_reads_zeros_behind_the_last_frame(engine, rate_in, channels):
     lib = engine._lib

@@ -175,7 +175,8 @@ def _as_wav(path, rate):
     return G.wav16(x, rate) if x.dtype == np.int16 else G.wav_f32(x, rate)
 
 
-ANALYZE = [(16000, 1, 1.0, None, 7.3), (16000, 1, 0.5, 0.95, 5.1), (48000, 2, 1.0, None, 6.7)]
+ANALYZE = [(16000, 1, 1.0, None, 7.3), (16000, 1, 0.5, 0.95, 5.1), (48000, 2, 1.0, None, 6.7), (48000, 6, 1.0, None, 6.7),
+           (16000, 3, 1.0, None, 7.3)]
 
 
 @pytest.mark.parametrize("case", range(len(ANALYZE)))
