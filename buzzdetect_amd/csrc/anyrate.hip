@@ -29,6 +29,7 @@
 // order of every addition is fixed by (ratio, j) alone: no atomics, no dependence on the launch around it.
 // Positions are 64-bit (j down exceeds 2^32).  bd_resample_any_host walks the same lanes in the same order on the host.
 #include "bd_internal.h"
+#include "bd_error.h"
 
 #include "../../include/buzzdetect_anyrate.h"
 
@@ -39,9 +40,6 @@
 #include <vector>
 
 namespace bd {
-
-void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
-
 namespace {
 
 constexpr int kArWaves = 4;
@@ -155,7 +153,7 @@ __global__ __launch_bounds__(kArThreads) void anyrate_kernel(const T* __restrict
     if (tid < nj) out[j0 + tid] = s_acc[tid];
 }
 
-// ---- design (engine.hip's design_taps at BD_RESAMPLE_HQ, oracle/resample_oracle.py taps(), as a function of u) ----
+// ---- design (resample_host.hip's design_taps at BD_RESAMPLE_HQ, oracle/resample_oracle.py taps(), as a function of u) ----
 double bessel_i0(double x) {
     double sum = 1.0, term = 1.0;
     for (int k = 1; k < 256; ++k) {

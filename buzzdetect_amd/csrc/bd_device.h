@@ -1,6 +1,6 @@
 // What the kernel files share: vector types, the f16 range guard, the split into f16 halves, the LDS swizzle, counted LDS
 // operations, the XCD-aware tile order, and the two host helpers every launcher with dynamic LDS needs.  Included by the kernel
-// .hip files (never by engine.hip); every file is its own translation unit, so everything sits in an anonymous namespace.
+// .hip files (never by the host files: engine.hip and the files engine_state.h lists); every file is its own translation unit, so everything sits in an anonymous namespace.
 #pragma once
 
 #include "bd_internal.h"

@@ -31,7 +31,7 @@ constexpr int mel_offset(int band) {          // index of band's first weight in
 }
 static_assert(mel_offset(BD_MEL_BANDS) == kMelNonZero, "mel pattern tables disagree");
 
-// Constant tables of the front end, built on the host at bd_create (engine.hip) and kept in
+// Constant tables of the front end, built on the host at bd_create (weights_fold.hip) and kept in
 // device memory.
 struct FeTables {
     float  hann[BD_STFT_WINDOW + 16];     // periodic Hann, evaluated in float32 like tf.signal.hann_window; zero past 400

@@ -20,6 +20,7 @@
 // only read, element offsets are 64-bit, and every index read from memory (a label, a row id, an offset) is brought into range
 // before it addresses anything.
 #include "bd_internal.h"
+#include "bd_error.h"
 #include "cluster_device.h"
 #include "dense_device.h"
 #include "simsearch_device.h"
@@ -33,9 +34,6 @@
 #pragma clang fp contract(off)
 
 namespace bd {
-
-void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -335,37 +333,26 @@ __global__ __launch_bounds__(kThreads) void cluster_stats_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-int refuse(const std::string& msg, int code = BD_EINVAL) {
-    set_error(msg);
-    return code;
-}
-
-int hip_result(const std::string& fn) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return BD_OK;
-    return refuse(fn + hipGetErrorString(e), BD_EHIP);
-}
-
 int check_rows(const std::string& fn, int64_t W) {
     if (W < 0 || W > BD_CLUSTER_MAX_ROWS)
-        return refuse(fn + "rows = " + std::to_string(W) + ", a call takes 0.." + std::to_string(BD_CLUSTER_MAX_ROWS));
+        return fail(BD_EINVAL, fn + "rows = " + std::to_string(W) + ", a call takes 0.." + std::to_string(BD_CLUSTER_MAX_ROWS));
     return BD_OK;
 }
 
 int check_clusters(const std::string& fn, int32_t K) {
     if (K < 1 || K > BD_CLUSTER_MAX_CLUSTERS)
-        return refuse(fn + "n_clusters = " + std::to_string(K) + ", allowed are 1.." + std::to_string(BD_CLUSTER_MAX_CLUSTERS));
+        return fail(BD_EINVAL, fn + "n_clusters = " + std::to_string(K) + ", allowed are 1.." + std::to_string(BD_CLUSTER_MAX_CLUSTERS));
     return BD_OK;
 }
 
 int check_metric(const std::string& fn, int32_t metric) {
-    if (metric != BD_CLUSTER_EUCLIDEAN && metric != BD_CLUSTER_COSINE) return refuse(fn + "unknown metric " + std::to_string(metric));
+    if (metric != BD_CLUSTER_EUCLIDEAN && metric != BD_CLUSTER_COSINE) return fail(BD_EINVAL, fn + "unknown metric " + std::to_string(metric));
     return BD_OK;
 }
 
 int check_pointer(const std::string& fn, const char* name, const void* p, int align) {
-    if (!p) return refuse(fn + name + " is null");
-    if ((uintptr_t)p % (uintptr_t)align) return refuse(fn + name + " is not " + std::to_string(align) + "-byte aligned");
+    if (!p) return fail(BD_EINVAL, fn + name + " is null");
+    if ((uintptr_t)p % (uintptr_t)align) return fail(BD_EINVAL, fn + name + " is not " + std::to_string(align) + "-byte aligned");
     return BD_OK;
 }
 
@@ -392,7 +379,7 @@ int check_workspace(const std::string& fn, const void* ws, int64_t bytes, const 
     const int rc = check_pointer(fn, "workspace_dev", ws, 16);
     if (rc != BD_OK) return rc;
     if (bytes < (int64_t)L.total)
-        return refuse(fn + "workspace_bytes = " + std::to_string(bytes) + ", needed are " + std::to_string(L.total), BD_EWORKSPACE);
+        return fail(BD_EWORKSPACE, fn + "workspace_bytes = " + std::to_string(bytes) + ", needed are " + std::to_string(L.total));
     return BD_OK;
 }
 
@@ -502,8 +489,8 @@ int bd_cluster_order_host(const int32_t* labels, int64_t rows, int32_t n_cluster
     if (rows == 0) return BD_OK;
     for (int64_t r = 0; r < rows; ++r)
         if (labels[r] < 0 || labels[r] >= n_clusters)
-            return bd::refuse(fn + "labels[" + std::to_string(r) + "] = " + std::to_string(labels[r]) + " is outside 0.." +
-                              std::to_string(n_clusters - 1), BD_ERANGE);
+            return bd::fail(BD_ERANGE, fn + "labels[" + std::to_string(r) + "] = " + std::to_string(labels[r]) + " is outside 0.." +
+                                           std::to_string(n_clusters - 1));
     std::vector<int32_t> cursor((size_t)n_clusters + 1, 0);
     for (int64_t r = 0; r < rows; ++r) ++cursor[(size_t)labels[r] + 1];
     for (int32_t j = 0; j < n_clusters; ++j) cursor[(size_t)j + 1] += cursor[j];
@@ -547,10 +534,10 @@ int bd_cluster_centroids_host(const float* e, int64_t rows, const float* n2, con
     if (rows == 0) return BD_OK;
     for (int32_t j = 0; j < n_clusters; ++j)
         if (offsets[j] < 0 || offsets[j] > offsets[j + 1] || offsets[j + 1] > rows)
-            return bd::refuse(fn + "offsets[" + std::to_string(j) + "..] do not ascend within 0.." + std::to_string(rows), BD_ERANGE);
+            return bd::fail(BD_ERANGE, fn + "offsets[" + std::to_string(j) + "..] do not ascend within 0.." + std::to_string(rows));
     for (int64_t i = offsets[0]; i < offsets[n_clusters]; ++i)
         if (order[i] < 0 || order[i] >= rows)
-            return bd::refuse(fn + "order[" + std::to_string(i) + "] = " + std::to_string(order[i]) + " is no row", BD_ERANGE);
+            return bd::fail(BD_ERANGE, fn + "order[" + std::to_string(i) + "] = " + std::to_string(order[i]) + " is no row");
     const int tiles = (n_clusters + 31) / 32;
     std::vector<float> sum(BD_CLUSTER_DIM), part(BD_CLUSTER_DIM);
     for (int32_t j = 0; j < 32 * tiles; ++j) {

@@ -12,7 +12,7 @@
 //
 // Nothing is added atomically, nothing is split over workgroups, the wide row is only read: the launch is idempotent and
 // bit-reproducible.
-#include "bd_internal.h"
+#include "engine_state.h"
 #include "ensemble_device.h"
 
 #include <cstring>
@@ -138,8 +138,6 @@ EnsOutput describe(const bd_ensemble_output& O, int wide_col, int width, int out
 
 }  // namespace
 
-void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
-
 int ensemble_build(const HeadSet& set, const bd_ensemble_output* outputs, int n_outputs, Ensemble* out, std::string* err) {
     const std::string fn = "bd_ensemble_attach: ";
     const int rc = check_outputs(fn, outputs, n_outputs, set.members, set.count.data(), err);
@@ -196,6 +194,40 @@ void launch_ensemble_combine(const Ensemble& ens, const float* wide, int ld_wide
 extern "C" {
 
 int bd_ensemble_abi_version(void) { return BD_ENSEMBLE_ABI_VERSION; }
+
+int bd_ensemble_count(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_ensemble_count: null handle");
+    return h->ens.n_outputs;
+}
+
+int bd_ensemble_outputs(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_ensemble_outputs: null handle");
+    return h->ens.columns;
+}
+
+int bd_ensemble_columns(bd_handle h, int32_t output, int32_t* first, int32_t* count) {
+    if (!h || !first || !count) return fail(BD_EINVAL, "bd_ensemble_columns: null argument");
+    if (output < 0 || output >= h->ens.n_outputs)
+        return fail(BD_EINVAL, "bd_ensemble_columns: output " + std::to_string(output) + " outside 0.." +
+                                   std::to_string(h->ens.n_outputs - 1));
+    *first = h->ens.first[output];
+    *count = h->ens.count[output];
+    return BD_OK;
+}
+
+int bd_ensemble_attach(bd_handle h, const bd_ensemble_output* outputs, int32_t n_outputs) {
+    if (!h || !outputs) return fail(BD_EINVAL, "bd_ensemble_attach: null argument");
+    if (!h->set.members) return fail(BD_EINVAL, "bd_ensemble_attach: the engine has no set of heads (bd_headset_attach comes first)");
+    if (h->ens.n_outputs) return fail(BD_EINVAL, "bd_ensemble_attach: the engine already has an ensemble");
+    BD_HIP(hipSetDevice(h->device));
+    std::string err;
+    bd::Ensemble ens;
+    const int rc = bd::ensemble_build(h->set, outputs, n_outputs, &ens, &err);
+    if (rc != BD_OK) return fail(rc, err);
+    h->ens = std::move(ens);
+    h->n_classes = h->ens.columns;
+    return BD_OK;
+}
 
 int bd_ensemble_combine_host(const float* wide, int64_t windows, int32_t ld_wide, const bd_ensemble_output* outputs, int32_t n_outputs,
                              const int32_t* member_first, float* out, int32_t ld_out) {

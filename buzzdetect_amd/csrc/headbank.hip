@@ -169,7 +169,7 @@ int copy_member(bd_bank_s* b, int32_t member, bool to_snapshot, void* stream_) {
     float *p = b->p + c.block, *snap = b->snap + c.block;
     hipLaunchKernelGGL(bank_copy_member_kernel, dim3(((kIn + 1) * b->s.C + 255) / 256), dim3(256), 0, stream, to_snapshot ? snap : p,
                        to_snapshot ? p : snap, b->s.C, c.ng, c.col0);
-    BD_TRAIN_HIP(hipGetLastError());
+    BD_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -218,7 +218,7 @@ int bd_bank_create(int device, const bd_head_layer* layers, int32_t n_members, i
     b->s = s;
     b->opt = *opt;
     b->members.assign(n_members, opt->learning_rate);
-    BD_TRAIN_HIP(hipMalloc(&b->pool, (size_t)total * sizeof(float)));
+    BD_HIP(hipMalloc(&b->pool, (size_t)total * sizeof(float)));
     float* at = b->pool;
     auto take = [&at](int64_t n) {
         float* p = at;
@@ -284,7 +284,7 @@ int bd_bank_step(bd_bank b, const float* X, int64_t ldx, const int32_t* rows, co
         hipLaunchKernelGGL(bd::bank_apply_kernel, dim3((n + 255) / 256, a.count), dim3(256), 0, stream, b->ws, slices, s, b->grad, b->p,
                            b->m, b->v, b->opt.kind, b->opt.beta_1, b->opt.beta_2, b->opt.epsilon, a);
     }
-    BD_TRAIN_HIP(hipGetLastError());
+    BD_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -312,7 +312,7 @@ int bd_bank_loss(bd_bank b, const float* X, int64_t ldx, const int32_t* rows, co
         hipLaunchKernelGGL(bd::bank_loss_sum_kernel, dim3(a.count), dim3(256), 0, stream, b->row_loss, B, s.max_batch,
                            bd::loss_scale(b->loss, B, s.C), loss_dev, (double*)nullptr, a);
     }
-    BD_TRAIN_HIP(hipGetLastError());
+    BD_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -330,7 +330,7 @@ int bd_bank_forward(bd_bank b, const float* X, int64_t ldx, const int32_t* rows,
     // group g's columns are members g mpg ..: columns g mpg C .. of a row of the caller's matrix, side by side as in the group
     hipLaunchKernelGGL(bd::bank_forward_kernel, dim3((B + 63) / 64, s.groups), dim3(256), 0, stream, X, ldx, rows, B, b->p, s, logits_dev,
                        (int64_t)s.mpg * s.C, (int)ldl);
-    BD_TRAIN_HIP(hipGetLastError());
+    BD_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -360,9 +360,9 @@ static int read_pair(bd_bank b, int32_t member, bool grad, float* w_host, float*
     const bd::Columns c = bd::columns_of(s, member);
     const float* src = (grad ? b->grad : b->p) + c.block + c.col0;
     if (w_host)
-        BD_TRAIN_HIP(hipMemcpy2D(w_host, (size_t)s.C * sizeof(float), src, (size_t)c.ng * sizeof(float), (size_t)s.C * sizeof(float),
+        BD_HIP(hipMemcpy2D(w_host, (size_t)s.C * sizeof(float), src, (size_t)c.ng * sizeof(float), (size_t)s.C * sizeof(float),
                                  bd::kIn, hipMemcpyDeviceToHost));
-    if (b_host) BD_TRAIN_HIP(hipMemcpy(b_host, src + (size_t)bd::kIn * c.ng, (size_t)s.C * sizeof(float), hipMemcpyDeviceToHost));
+    if (b_host) BD_HIP(hipMemcpy(b_host, src + (size_t)bd::kIn * c.ng, (size_t)s.C * sizeof(float), hipMemcpyDeviceToHost));
     return BD_OK;
 }
 

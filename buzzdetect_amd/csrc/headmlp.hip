@@ -18,8 +18,10 @@
 // Four super-steps (32 k) are in flight ahead of the sixteen matrix instructions that use them; one accumulator per wave is
 // enough, the instruction's issue interval and its dependent latency both being 64 cycles.  A workgroup is 2 x 2 waves = a
 // 64 x 64 tile, so 1024 windows x 1024 columns are 256 workgroups, one per compute unit.  There is no LDS and no barrier.
-#include "bd_internal.h"
+#include "engine_state.h"
 #include "dense_device.h"
+
+#include <cstring>
 
 #include "../../include/buzzdetect_head.h"
 
@@ -84,3 +86,68 @@ void launch_softmax_rows(const float* x, int ldx, float* y, int windows, int n, 
 }
 
 }  // namespace bd
+
+extern "C" {
+
+int bd_head_abi_version(void) { return BD_HEAD_ABI_VERSION; }
+
+int bd_head_outputs(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_head_outputs: null handle");
+    return h->stack.empty() ? 0 : h->stack.back().n;
+}
+
+int bd_head_attach(bd_handle h, const bd_head_layer* layers, int32_t n_layers) {
+    if (!h || !layers) return fail(BD_EINVAL, "bd_head_attach: null argument");
+    if (h->n_classes != 0 || !h->stack.empty())
+        return fail(BD_EINVAL, "bd_head_attach: the engine already has a head (create it with n_classes == 0)");
+    if (n_layers < 1 || n_layers > BD_HEAD_MAX_LAYERS)
+        return fail(BD_EINVAL, "bd_head_attach: a stack has 1.." + std::to_string(BD_HEAD_MAX_LAYERS) + " layers, not " +
+                                   std::to_string(n_layers));
+    int width = BD_EMBEDDING_SIZE;
+    size_t floats = 0;
+    for (int i = 0; i < n_layers; ++i) {
+        const bd_head_layer& L = layers[i];
+        const std::string who = "bd_head_attach: layer " + std::to_string(i);
+        if (!L.kernel) return fail(BD_EINVAL, who + " has no kernel");
+        if (L.n_out < 1 || L.n_out > BD_HEAD_MAX_WIDTH)
+            return fail(BD_EINVAL, who + ": width " + std::to_string(L.n_out) + " outside 1.." + std::to_string(BD_HEAD_MAX_WIDTH));
+        if (L.n_in != width)
+            return fail(BD_EINVAL, who + " takes " + std::to_string(L.n_in) + " inputs, the layer before it gives " +
+                                       std::to_string(width));
+        if (L.activation < BD_HEAD_LINEAR || L.activation > BD_HEAD_SOFTMAX)
+            return fail(BD_EINVAL, who + ": unknown activation " + std::to_string(L.activation));
+        if (L.activation == BD_HEAD_SOFTMAX && i + 1 != n_layers) return fail(BD_EINVAL, who + ": softmax on a hidden layer");
+        floats += bd::dense_packed_floats(L.n_in, L.n_out) + (size_t)align_up(L.n_out, 4);
+        width = L.n_out;
+    }
+    std::vector<float> host(floats, 0.0f);
+    std::vector<bd::DenseLayer> stack;
+    std::vector<size_t> at;
+    size_t off = 0;
+    for (int i = 0; i < n_layers; ++i) {
+        const bd_head_layer& L = layers[i];
+        at.push_back(off);
+        bd::dense_pack_weights(L.kernel, L.n_in, L.n_out, host.data() + off);
+        off += bd::dense_packed_floats(L.n_in, L.n_out);
+        if (L.bias) std::memcpy(host.data() + off, L.bias, (size_t)L.n_out * sizeof(float));
+        off += (size_t)align_up(L.n_out, 4);
+    }
+    BD_HIP(hipSetDevice(h->device));
+    float* dev = nullptr;
+    BD_HIP(hipMalloc(&dev, floats * sizeof(float)));
+    if (hipMemcpy(dev, host.data(), floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(BD_EHIP, "bd_head_attach: upload failed");
+    }
+    for (int i = 0; i < n_layers; ++i) {
+        const bd_head_layer& L = layers[i];
+        stack.push_back(bd::DenseLayer{L.n_in, L.n_out, L.activation, dev + at[i],
+                                       dev + at[i] + bd::dense_packed_floats(L.n_in, L.n_out)});
+    }
+    h->d_stack = dev;
+    h->stack = std::move(stack);
+    h->n_classes = width;
+    return BD_OK;
+}
+
+}  // extern "C"

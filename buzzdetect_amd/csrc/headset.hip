@@ -18,7 +18,7 @@
 // loads reach round_up(K, 32) columns; those at k >= K are replaced by zero, never used); a last layer in front of a softmax
 // writes region 2, packed, where no later depth writes; every other last layer writes its member's columns of the logits.
 // Nothing is split over workgroups, nothing is added atomically, every launch is idempotent.
-#include "bd_internal.h"
+#include "engine_state.h"
 #include "dense_device.h"
 
 #include <cstring>
@@ -314,3 +314,45 @@ void launch_head_set(const HeadSet& set, const float* pooled, float* logits, int
 }
 
 }  // namespace bd
+
+extern "C" {
+
+int bd_headset_abi_version(void) { return BD_HEADSET_ABI_VERSION; }
+
+int bd_headset_members(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_headset_members: null handle");
+    return h->set.members;
+}
+
+int bd_headset_outputs(bd_handle h) {
+    if (!h) return fail(BD_EINVAL, "bd_headset_outputs: null handle");
+    return h->set.outputs;
+}
+
+int bd_headset_columns(bd_handle h, int32_t member, int32_t* first, int32_t* count) {
+    if (!h || !first || !count) return fail(BD_EINVAL, "bd_headset_columns: null argument");
+    if (member < 0 || member >= h->set.members)
+        return fail(BD_EINVAL, "bd_headset_columns: member " + std::to_string(member) + " outside 0.." +
+                                   std::to_string(h->set.members - 1));
+    *first = h->set.first[member];
+    *count = h->set.count[member];
+    return BD_OK;
+}
+
+int bd_headset_attach(bd_handle h, const bd_headset_member* members, int32_t n_members) {
+    if (!h || !members) return fail(BD_EINVAL, "bd_headset_attach: null argument");
+    if (h->set.members) return fail(BD_EINVAL, "bd_headset_attach: the engine already has a set of heads");
+    if (!h->stack.empty()) return fail(BD_EINVAL, "bd_headset_attach: the engine already has a stack (bd_head_attach)");
+    if (h->n_classes != 0)
+        return fail(BD_EINVAL, "bd_headset_attach: the engine already has a head (create it with n_classes == 0)");
+    BD_HIP(hipSetDevice(h->device));
+    std::string err;
+    bd::HeadSet set;
+    const int rc = bd::headset_build(members, n_members, &set, &err);
+    if (rc != BD_OK) return fail(rc, err);
+    h->set = std::move(set);
+    h->n_classes = h->set.outputs;
+    return BD_OK;
+}
+
+}  // extern "C"

@@ -202,7 +202,7 @@ int bd_trainer_create(int device, const bd_head_layer* layers, int32_t n_layers,
     t->ws_floats = bd::slices_of(max_batch) * t->s.params_max;
     const int64_t off_ws = t->s.floats, off_rl = off_ws + bd::up64(t->ws_floats), off_acc = off_rl + bd::up64(max_batch);
     const int64_t total = off_acc + 64;
-    BD_TRAIN_HIP(hipMalloc(&t->pool, (size_t)total * sizeof(float)));
+    BD_HIP(hipMalloc(&t->pool, (size_t)total * sizeof(float)));
     hipError_t err = hipMemset(t->pool, 0, (size_t)total * sizeof(float));
     if (err == hipSuccess) err = bd::upload_stack(t->pool, t->s, layers);
     if (err != hipSuccess) {
@@ -268,7 +268,7 @@ static int do_step(bd_trainer t, const float* X, int64_t ldx, const int32_t* row
         hipLaunchKernelGGL(bd::apply_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, t->ws, slices, n, pool + L.grad, pool + L.p,
                            bd::slot(pool, L.m), bd::slot(pool, L.v), u);
     }
-    BD_TRAIN_HIP(hipGetLastError());
+    BD_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -290,7 +290,7 @@ static int do_loss(bd_trainer t, const float* X, int64_t ldx, const int32_t* row
     if ((rc = bd::enter(t, stream_, &stream)) < 0) return rc;
     bd::enqueue_forward(t, X, ldx, rows, B, stream);
     bd::enqueue_loss(t, targets, row_w, B, loss_dev, false, false, stream);
-    BD_TRAIN_HIP(hipGetLastError());
+    BD_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -350,7 +350,7 @@ int bd_trainer_logits(bd_trainer t, int32_t B, float* logits_host) {
     const int rc = bd::enter_and_wait(t);
     if (rc < 0) return rc;
     const bd::StackLayer& L = t->s.last();
-    BD_TRAIN_HIP(hipMemcpy2D(logits_host, (size_t)L.n * sizeof(float), t->pool + L.y, (size_t)L.ld * sizeof(float),
+    BD_HIP(hipMemcpy2D(logits_host, (size_t)L.n * sizeof(float), t->pool + L.y, (size_t)L.ld * sizeof(float),
                         (size_t)L.n * sizeof(float), B, hipMemcpyDeviceToHost));
     return BD_OK;
 }

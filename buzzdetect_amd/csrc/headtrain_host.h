@@ -12,6 +12,7 @@
 #define BD_HEADTRAIN_HOST_H
 
 #include "headtrain_device.h"
+#include "bd_error.h"
 
 #include <cstring>
 #include <memory>
@@ -19,23 +20,9 @@
 #include <vector>
 
 namespace bd {
-
-void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
-
 namespace {
 
 using namespace train;
-
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
-#define BD_TRAIN_HIP(expr)                                                                         \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(BD_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // ---- a launch's members ----
 
@@ -116,7 +103,7 @@ struct TrainHandle {
 
 // the prologue of a call that enqueues: the handle's device, the caller's stream, remembered for the calls that wait
 int enter(TrainHandle* h, void* stream_, hipStream_t* stream) {
-    BD_TRAIN_HIP(hipSetDevice(h->device));
+    BD_HIP(hipSetDevice(h->device));
     *stream = (hipStream_t)stream_;
     h->last = *stream;
     return BD_OK;
@@ -124,8 +111,8 @@ int enter(TrainHandle* h, void* stream_, hipStream_t* stream) {
 
 // the prologue of a call that reads: the handle's device, everything enqueued so far done
 int enter_and_wait(const TrainHandle* h) {
-    BD_TRAIN_HIP(hipSetDevice(h->device));
-    BD_TRAIN_HIP(hipStreamSynchronize(h->last));
+    BD_HIP(hipSetDevice(h->device));
+    BD_HIP(hipStreamSynchronize(h->last));
     return BD_OK;
 }
 
@@ -168,10 +155,10 @@ int select_device(const std::string& who, int device) {
         return fail(BD_ENODEVICE, who + ": no HIP device visible (this library has no CPU path)");
     if (device < 0 || device >= count) return fail(BD_ENODEVICE, who + ": device index out of range");
     hipDeviceProp_t prop;
-    BD_TRAIN_HIP(hipGetDeviceProperties(&prop, device));
+    BD_HIP(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(BD_ENODEVICE, who + ": kernels are built for gfx950 only, device is " + prop.gcnArchName);
-    BD_TRAIN_HIP(hipSetDevice(device));
+    BD_HIP(hipSetDevice(device));
     return BD_OK;
 }
 
@@ -313,7 +300,7 @@ int copy_stack(float* block, const StackLayout& s, bool to_snapshot, hipStream_t
     for (int l = 0; l < s.n_layers; ++l) {
         const StackLayer& L = s.layers[l];
         float *p = block + L.p, *snap = block + L.snap;
-        BD_TRAIN_HIP(hipMemcpyAsync(to_snapshot ? snap : p, to_snapshot ? p : snap, (size_t)L.params() * sizeof(float),
+        BD_HIP(hipMemcpyAsync(to_snapshot ? snap : p, to_snapshot ? p : snap, (size_t)L.params() * sizeof(float),
                                     hipMemcpyDeviceToDevice, stream));
     }
     return BD_OK;
@@ -324,8 +311,8 @@ int read_stack_pair(const TrainHandle* h, const float* block, const StackLayer& 
     const int rc = enter_and_wait(h);
     if (rc < 0) return rc;
     const float* src = block + (grad ? L.grad : L.p);
-    if (w_host) BD_TRAIN_HIP(hipMemcpy(w_host, src, (size_t)L.k * L.n * sizeof(float), hipMemcpyDeviceToHost));
-    if (b_host) BD_TRAIN_HIP(hipMemcpy(b_host, src + (size_t)L.k * L.n, (size_t)L.n * sizeof(float), hipMemcpyDeviceToHost));
+    if (w_host) BD_HIP(hipMemcpy(w_host, src, (size_t)L.k * L.n * sizeof(float), hipMemcpyDeviceToHost));
+    if (b_host) BD_HIP(hipMemcpy(b_host, src + (size_t)L.k * L.n, (size_t)L.n * sizeof(float), hipMemcpyDeviceToHost));
     return BD_OK;
 }
 
@@ -337,9 +324,9 @@ int mean_losses(const TrainHandle* h, int32_t reset, float* mean_host, const cha
     if (rc < 0) return rc;
     const int M = h->members.size();
     std::vector<double> acc(2 * (size_t)M, 0.0);
-    BD_TRAIN_HIP(hipMemcpy(acc.data(), h->acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    BD_HIP(hipMemcpy(acc.data(), h->acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int mb = 0; mb < M; ++mb) mean_host[mb] = acc[2 * mb + 1] > 0.0 ? (float)(acc[2 * mb] / acc[2 * mb + 1]) : 0.0f;
-    if (reset) BD_TRAIN_HIP(hipMemset(h->acc, 0, acc.size() * sizeof(double)));
+    if (reset) BD_HIP(hipMemset(h->acc, 0, acc.size() * sizeof(double)));
     return BD_OK;
 }
 
@@ -352,8 +339,8 @@ int workspace_fill(const TrainHandle* h, uint32_t pattern, const char* who) {
     if (!h) return fail(BD_EINVAL, std::string(who) + ": null handle");
     const int rc = enter_and_wait(h);
     if (rc < 0) return rc;
-    BD_TRAIN_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(h->ws), (int)pattern, (size_t)h->ws_floats));
-    BD_TRAIN_HIP(hipDeviceSynchronize());
+    BD_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(h->ws), (int)pattern, (size_t)h->ws_floats));
+    BD_HIP(hipDeviceSynchronize());
     return BD_OK;
 }
 
@@ -361,7 +348,7 @@ int workspace_read(const TrainHandle* h, float* host, int64_t floats, const char
     if (!h || !host || floats < 0 || floats > h->ws_floats) return fail(BD_EINVAL, std::string(who) + ": bad argument");
     const int rc = enter_and_wait(h);
     if (rc < 0) return rc;
-    BD_TRAIN_HIP(hipMemcpy(host, h->ws, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost));
+    BD_HIP(hipMemcpy(host, h->ws, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost));
     return BD_OK;
 }
 

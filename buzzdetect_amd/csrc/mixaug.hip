@@ -25,6 +25,7 @@
 // -fhip-fp32-correctly-rounded-divide-sqrt.  Contraction is switched off for the whole file, so that no product spelled `*`
 // (which is all __fmul_rn is in that header) can fuse with an addition on one side and not on the other.
 #include "bd_internal.h"
+#include "bd_error.h"
 
 #include "../../include/buzzdetect_mix.h"
 
@@ -36,9 +37,6 @@
 #pragma clang fp contract(off)
 
 namespace bd {
-
-void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
-
 namespace {
 
 constexpr int kMixThreads = 256;

@@ -21,11 +21,8 @@
 #include <string>
 
 #include "bd_internal.h"
+#include "bd_error.h"
 #include "../../include/buzzdetect_pcm.h"
-
-namespace bd {
-void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
-}
 
 namespace {
 

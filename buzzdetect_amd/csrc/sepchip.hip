@@ -183,7 +183,7 @@ __global__ __launch_bounds__(512, 2) void sep_chip_kernel(const ChipChain ch, co
         *reinterpret_cast<u32x2*>(p_) = u32x2{PK[2 * (J)], PK[2 * (J) + 1]};                              \
         *reinterpret_cast<u32x2*>(p_ + kTrHalfBytes) = u32x2{PK[24 + 2 * (J)], PK[25 + 2 * (J)]};         \
     }
-    // taps [9][512] and shift [512] of a layer are one [10][512] table (engine.hip lays dw_b16 behind dw_w16; the launcher checks)
+    // taps [9][512] and shift [512] of a layer are one [10][512] table (weights_fold.hip lays dw_b16 behind dw_w16; the launcher checks)
 #define CHIP_TAPS_RSRC(DW_W) __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DW_W), 0, 10 * K * 4, 0x00020000)
 
     // ---------------------------------------------------------------------- the K loop of one layer (KQ_C: k16 steps), the
@@ -606,7 +606,7 @@ void launch_chip(const float* in, float* out, const SepLayer* L, int nl, long lo
 // checked the shapes (launch_separable_run_next_dw below).  With `next` (the stride-2 layer behind the run) the run's output is not written:
 // next's depthwise is applied in the epilogue and out = [windows][3][2][512] (then `out` must not be `in`: the tiles' rows
 // differ).  False (nothing launched) when a layer's shift table does not follow its taps (the kernel reads both through
-// one [10][512] resource; engine.hip lays dw_b16 behind dw_w16).
+// one [10][512] resource; weights_fold.hip lays dw_b16 behind dw_w16).
 // planes (with next): the output leaves as f16 hi / lo planes [windows * 6][512] (hi at out, lo behind it), what septail.hip reads.
 static bool launch_separable_chip(const float* in, float* out, int windows, const SepLayer* L, int nl, hipStream_t stream,
                                   const SepLayer* next, bool planes) {

@@ -18,6 +18,7 @@
 // Nothing is added atomically in global memory, no result depends on the grid, every output element has one writer, and inputs are only read:
 // the launches are idempotent apart from the state, which bd_search_update advances by design.
 #include "bd_internal.h"
+#include "bd_error.h"
 #include "dense_device.h"
 #include "simsearch_device.h"
 
@@ -31,9 +32,6 @@
 #pragma clang fp contract(off)
 
 namespace bd {
-
-void set_error(const std::string& msg);     // engine.hip: the text bd_last_error() returns on this thread
-
 namespace {
 
 constexpr int kSearchThreads = 256;
@@ -159,20 +157,15 @@ __global__ __launch_bounds__(kSearchThreads) void search_update_kernel(const flo
     for (int i = tid; i < k; i += kSearchThreads) state[i] = buf[i];
 }
 
-int refuse(const std::string& msg, int code = BD_EINVAL) {
-    set_error(msg);
-    return code;
-}
-
 int check_windows(const std::string& fn, int64_t W) {
     if (W < 0 || W > BD_SEARCH_MAX_WINDOWS)
-        return refuse(fn + "windows = " + std::to_string(W) + ", a call takes 0.." + std::to_string(BD_SEARCH_MAX_WINDOWS));
+        return fail(BD_EINVAL, fn + "windows = " + std::to_string(W) + ", a call takes 0.." + std::to_string(BD_SEARCH_MAX_WINDOWS));
     return BD_OK;
 }
 
 int check_queries(const std::string& fn, int32_t Q) {
     if (Q < 1 || Q > BD_SEARCH_MAX_QUERIES)
-        return refuse(fn + "n_queries = " + std::to_string(Q) + ", allowed are 1.." + std::to_string(BD_SEARCH_MAX_QUERIES));
+        return fail(BD_EINVAL, fn + "n_queries = " + std::to_string(Q) + ", allowed are 1.." + std::to_string(BD_SEARCH_MAX_QUERIES));
     return BD_OK;
 }
 
@@ -181,21 +174,15 @@ int check_update(const std::string& fn, const float* scores, int64_t W, int32_t 
                  int64_t base_id, const uint64_t* keys, int32_t k) {
     int rc = check_queries(fn, Q);
     if (rc != BD_OK) return rc;
-    if (k < 1 || k > BD_SEARCH_MAX_K) return refuse(fn + "k = " + std::to_string(k) + ", allowed are 1.." + std::to_string(BD_SEARCH_MAX_K));
+    if (k < 1 || k > BD_SEARCH_MAX_K) return fail(BD_EINVAL, fn + "k = " + std::to_string(k) + ", allowed are 1.." + std::to_string(BD_SEARCH_MAX_K));
     if ((rc = check_windows(fn, W)) != BD_OK) return rc;
-    if (base_id < 0) return refuse(fn + "base_id = " + std::to_string(base_id) + " is negative");
+    if (base_id < 0) return fail(BD_EINVAL, fn + "base_id = " + std::to_string(base_id) + " is negative");
     if (base_id + W > 0xFFFFFFFFll)
-        return refuse(fn + "base_id + windows = " + std::to_string(base_id + W) + " is past the last id, 4294967295", BD_ERANGE);
-    if (row_stride == 0 || col_stride == 0) return refuse(fn + (row_stride == 0 ? "row_stride" : "col_stride") + " is 0");
-    if (!keys) return refuse(fn + "keys is null");
-    if (W > 0 && !scores) return refuse(fn + "scores is null");
+        return fail(BD_ERANGE, fn + "base_id + windows = " + std::to_string(base_id + W) + " is past the last id, 4294967295");
+    if (row_stride == 0 || col_stride == 0) return fail(BD_EINVAL, fn + (row_stride == 0 ? "row_stride" : "col_stride") + " is 0");
+    if (!keys) return fail(BD_EINVAL, fn + "keys is null");
+    if (W > 0 && !scores) return fail(BD_EINVAL, fn + "scores is null");
     return BD_OK;
-}
-
-int hip_result(const std::string& fn) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return BD_OK;
-    return refuse(fn + hipGetErrorString(e), BD_EHIP);
 }
 
 }  // namespace
@@ -215,7 +202,7 @@ int bd_search_pack_queries(const float* queries, int32_t n_queries, float* packe
     const std::string fn = "bd_search_pack_queries: ";
     const int rc = bd::check_queries(fn, n_queries);
     if (rc != BD_OK) return rc;
-    if (!queries || !packed) return bd::refuse(fn + (queries ? "packed" : "queries") + " is null");
+    if (!queries || !packed) return bd::fail(BD_EINVAL, fn + (queries ? "packed" : "queries") + " is null");
     std::vector<float> kernel((size_t)BD_SEARCH_DIM * n_queries);        // [K][N], as a Dense layer's kernel
     for (int q = 0; q < n_queries; ++q)
         for (int c = 0; c < BD_SEARCH_DIM; ++c) kernel[(size_t)c * n_queries + q] = queries[(size_t)q * BD_SEARCH_DIM + c];
@@ -228,8 +215,8 @@ int bd_search_norms(const float* e_dev, int64_t windows, float* n2_dev, void* st
     const int rc = bd::check_windows(fn, windows);
     if (rc != BD_OK) return rc;
     if (windows == 0) return BD_OK;
-    if (!e_dev || !n2_dev) return bd::refuse(fn + (e_dev ? "n2_dev" : "e_dev") + " is null");
-    if ((uintptr_t)e_dev % 4 || (uintptr_t)n2_dev % 4) return bd::refuse(fn + "misaligned buffer");
+    if (!e_dev || !n2_dev) return bd::fail(BD_EINVAL, fn + (e_dev ? "n2_dev" : "e_dev") + " is null");
+    if ((uintptr_t)e_dev % 4 || (uintptr_t)n2_dev % 4) return bd::fail(BD_EINVAL, fn + "misaligned buffer");
     hipLaunchKernelGGL(bd::search_norms_kernel, dim3((unsigned)((windows + 3) / 4)), dim3(bd::kSearchThreads), 0,
                        static_cast<hipStream_t>(stream), e_dev, (int)windows, n2_dev);
     return bd::hip_result(fn);
@@ -240,7 +227,7 @@ int bd_search_norms_host(const float* e, int64_t windows, float* n2) {
     const int rc = bd::check_windows(fn, windows);
     if (rc != BD_OK) return rc;
     if (windows == 0) return BD_OK;
-    if (!e || !n2) return bd::refuse(fn + (e ? "n2" : "e") + " is null");
+    if (!e || !n2) return bd::fail(BD_EINVAL, fn + (e ? "n2" : "e") + " is null");
     for (int64_t w = 0; w < windows; ++w) {
         float v[64];
         for (int lane = 0; lane < 64; ++lane) v[lane] = bd::search::norm_chain(e + (size_t)w * BD_SEARCH_DIM, lane);
@@ -255,14 +242,14 @@ int bd_search_scores(const float* e_dev, int64_t windows, const float* packed_de
     int rc = bd::check_queries(fn, n_queries);
     if (rc != BD_OK) return rc;
     if ((rc = bd::check_windows(fn, windows)) != BD_OK) return rc;
-    if (metric != BD_SEARCH_DOT && metric != BD_SEARCH_COSINE) return bd::refuse(fn + "unknown metric " + std::to_string(metric));
-    if (row_stride == 0 || col_stride == 0) return bd::refuse(fn + (row_stride == 0 ? "row_stride" : "col_stride") + " is 0");
-    if (!packed_dev || (uintptr_t)packed_dev % 16) return bd::refuse(fn + "packed_dev is null or not 16-byte aligned");
+    if (metric != BD_SEARCH_DOT && metric != BD_SEARCH_COSINE) return bd::fail(BD_EINVAL, fn + "unknown metric " + std::to_string(metric));
+    if (row_stride == 0 || col_stride == 0) return bd::fail(BD_EINVAL, fn + (row_stride == 0 ? "row_stride" : "col_stride") + " is 0");
+    if (!packed_dev || (uintptr_t)packed_dev % 16) return bd::fail(BD_EINVAL, fn + "packed_dev is null or not 16-byte aligned");
     if (windows == 0) return BD_OK;
-    if (!e_dev || (uintptr_t)e_dev % 16) return bd::refuse(fn + "e_dev is null or not 16-byte aligned");
-    if (!scores_dev || (uintptr_t)scores_dev % 4) return bd::refuse(fn + "scores_dev is null or misaligned");
+    if (!e_dev || (uintptr_t)e_dev % 16) return bd::fail(BD_EINVAL, fn + "e_dev is null or not 16-byte aligned");
+    if (!scores_dev || (uintptr_t)scores_dev % 4) return bd::fail(BD_EINVAL, fn + "scores_dev is null or misaligned");
     if (metric == BD_SEARCH_COSINE && (!n2_dev || (uintptr_t)n2_dev % 4))
-        return bd::refuse(fn + "n2_dev is null or misaligned (BD_SEARCH_COSINE reads the rows' squared norms)");
+        return bd::fail(BD_EINVAL, fn + "n2_dev is null or misaligned (BD_SEARCH_COSINE reads the rows' squared norms)");
     hipLaunchKernelGGL(bd::search_scores_kernel, dim3((unsigned)((windows + 63) / 64), (unsigned)((n_queries + 63) / 64)),
                        dim3(bd::kSearchThreads), 0, static_cast<hipStream_t>(stream), e_dev, (int)windows,
                        reinterpret_cast<const float4*>(packed_dev), (int)n_queries, (int)metric, n2_dev, scores_dev,
@@ -275,7 +262,7 @@ int bd_search_update(const float* scores_dev, int64_t windows, int32_t n_queries
     const std::string fn = "bd_search_update: ";
     const int rc = bd::check_update(fn, scores_dev, windows, n_queries, row_stride, col_stride, base_id, keys_dev, k);
     if (rc != BD_OK) return rc;
-    if ((uintptr_t)keys_dev % 8 || (uintptr_t)scores_dev % 4) return bd::refuse(fn + "misaligned buffer");
+    if ((uintptr_t)keys_dev % 8 || (uintptr_t)scores_dev % 4) return bd::fail(BD_EINVAL, fn + "misaligned buffer");
     if (windows == 0) return BD_OK;
     hipLaunchKernelGGL(bd::search_update_kernel, dim3((unsigned)n_queries), dim3(bd::kSearchThreads), 0,
                        static_cast<hipStream_t>(stream), scores_dev, (int)windows, (long long)row_stride, (long long)col_stride,
@@ -304,7 +291,7 @@ int bd_search_update_host(const float* scores, int64_t windows, int32_t n_querie
 }
 
 int64_t bd_search_decode_host(const uint64_t* keys, int64_t n, float* scores, uint32_t* ids) {
-    if (n < 0 || (n > 0 && (!keys || !scores || !ids))) return bd::refuse("bd_search_decode_host: null argument or n negative");
+    if (n < 0 || (n > 0 && (!keys || !scores || !ids))) return bd::fail(BD_EINVAL, "bd_search_decode_host: null argument or n negative");
     int64_t real = 0;
     for (int64_t i = 0; i < n; ++i) {
         if (keys[i]) {

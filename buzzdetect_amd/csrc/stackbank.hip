@@ -214,7 +214,7 @@ int bd_stackbank_create(int device, const bd_head_layer* layers, int32_t n_membe
     b->max_batch = max_batch;
     b->opt = *opt;
     b->members.assign(n_members, opt->learning_rate);
-    BD_TRAIN_HIP(hipMalloc(&b->pool, (size_t)pool_floats * sizeof(float)));
+    BD_HIP(hipMalloc(&b->pool, (size_t)pool_floats * sizeof(float)));
     b->ws = b->pool + b->stride * n_members;
     b->acc = reinterpret_cast<double*>(b->ws + b->ws_floats);
     hipError_t err = hipMemset(b->pool, 0, (size_t)pool_floats * sizeof(float));
@@ -264,7 +264,7 @@ int bd_stackbank_step(bd_stackbank b, const float* X, int64_t ldx, const int32_t
                                b->opt.beta_1, b->opt.beta_2, b->opt.epsilon, a);
         }
     }
-    BD_TRAIN_HIP(hipGetLastError());
+    BD_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -282,7 +282,7 @@ int bd_stackbank_loss(bd_stackbank b, const float* X, int64_t ldx, const int32_t
         bd::enqueue_forward(b, X, ldx, rows, B, a, nullptr, 0, 0, stream);
         bd::enqueue_loss(b, targets, row_w, ldw, B, loss_dev, false, a, stream);
     }
-    BD_TRAIN_HIP(hipGetLastError());
+    BD_HIP(hipGetLastError());
     return BD_OK;
 }
 
@@ -299,7 +299,7 @@ int bd_stackbank_forward(bd_stackbank b, const float* X, int64_t ldx, const int3
     if ((rc = bd::enter(b, stream_, &stream)) < 0) return rc;
     for (int first = 0; first < b->M; first += bd::kMembersPerLaunch)
         bd::enqueue_forward(b, X, ldx, rows, B, bd::members_from(b->M, first), logits_dev, C, (int)ldl, stream);
-    BD_TRAIN_HIP(hipGetLastError());
+    BD_HIP(hipGetLastError());
     return BD_OK;
 }
 

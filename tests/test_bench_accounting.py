@@ -10,7 +10,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import bench
 from oracle import yamnet_oracle as O
 
-# profile slots that see a launch per batch (engine.hip run_chunks): slot 2 l + 1 is layer l + 2's pointwise / fused kernel
+# profile slots that see a launch per batch (engine_pass.hip run_chunks): slot 2 l + 1 is layer l + 2's pointwise / fused kernel
 DEFAULT = [0, 5, 7, 13, 23, 25, 27, 28]                               # layers 5-7 one launch (slot 13), layers 8-12 + depthwise 13 one (slot 23), the tail (25, 27)
 NO_MID = [0, 5, 7, 9, 11, 13, 23, 25, 27, 28]                         # bd_set_fusion separable = 10: layers 5-7 on their four kernels
 PER_OP = list(range(0, 29))                                           # bd_set_fusion 0 / 0: conv1, every depthwise, every 1x1, pool + head

@@ -272,7 +272,7 @@ def test_one_hour_file_in_batches_of_1024(engine, weights_bundle):
 
 # --------------------------------------------------------------------------- pointwise GEMM in isolation
 def _pow2_operands(a, wt):
-    """What bd_create / the calibration do to the operands of a 1x1 convolution (engine.hip, SepLayer in bd_internal.h),
+    """What bd_create / the calibration do to the operands of a 1x1 convolution (weights_fold.hip, engine_pass.hip, SepLayer in bd_internal.h),
     restated: activations times the power of two that puts their largest into [2^8, 2^9), every weight row times the one
     that puts its largest into [2^12, 2^13), f16 hi + lo of the scaled weights, and the epilogue's inverse factors."""
     import torch

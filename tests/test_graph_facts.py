@@ -148,11 +148,12 @@ def test_library_constants_match_the_graph(facts):
     assert consts["BD_FFT_LENGTH"] == _const(g, "stft/fft_length")
     assert consts["BD_PATCH_FRAMES"] == _const(g, "frame/frame_length")
     assert ["int32", consts["BD_MIN_SAMPLES"]] in g["main_graph_scalar_consts"]
-    src = open(os.path.join(os.path.dirname(HERE), "buzzdetect_amd", "csrc", "engine.hip")).read()
+    csrc = os.path.join(os.path.dirname(HERE), "buzzdetect_amd", "csrc")
+    src = open(os.path.join(csrc, "engine_state.h")).read()
     table = re.search(r"kLayerDefs\[14\]\[2\] = \{(.*?)\};", src, flags=re.S).group(1)
     pairs = [tuple(int(x) for x in p) for p in re.findall(r"\{(\d+),\s*(\d+)\}", table)]
     assert tuple(pairs) == O.LAYER_DEFS
-    assert "1e-4" in src                                           # fold_bn's epsilon
+    assert "1e-4" in open(os.path.join(csrc, "weights_fold.hip")).read()     # fold_bn's epsilon
 
 
 @pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")

@@ -14,7 +14,7 @@ from tools import record_train_refusals as R
 
 SOURCES = ("headtrain.hip", "headbank.hip", "stackbank.hip")
 # what headtrain_host.h defines for all three: functions, then types, then the rest
-SHARED_FUNCTIONS = ("fail", "check_training_setup", "check_stack", "select_device", "check_member", "check_batch", "check_row_weights",
+SHARED_FUNCTIONS = ("check_training_setup", "check_stack", "select_device", "check_member", "check_batch", "check_row_weights",
                     "adam_rate", "members_from", "set_learning_rate", "set_weight_decay", "set_frozen", "snapshot_member",
                     "restore_member", "loss_inv", "loss_scale", "slices_of", "up64", "stack_layout", "upload_stack", "copy_stack",
                     "read_stack_pair", "mean_losses", "workspace_floats", "workspace_fill", "workspace_read", "destroy", "enter",
@@ -55,10 +55,15 @@ def test_no_training_file_defines_a_shared_routine_again():
         assert defines_function(name, header), f"headtrain_host.h does not define {name}"
     for name in SHARED_TYPES:
         assert re.search(r"\bstruct " + name + r"\b[^;]*\{", header), name
-    assert len(re.findall(r"#define \w+_HIP\(", header)) == 1 and "kMembersPerLaunch =" in header
+    # fail and the HIP-check macro are the whole library's one copy (bd_error.h), which the header includes and does not repeat
+    errors = read("bd_error.h")
+    assert '#include "bd_error.h"' in header and "bd_error.h" in build.HEADERS
+    assert defines_function("fail", errors) and not defines_function("fail", header)
+    assert len(re.findall(r"#define \w+_HIP\(", errors)) == 1 and not re.search(r"#define \w+_HIP\(", header)
+    assert "kMembersPerLaunch =" in header and "set_error(const" not in header
     for source in SOURCES:
         text = read(source)
-        for name in SHARED_FUNCTIONS + FORMER_COPIES:
+        for name in SHARED_FUNCTIONS + ("fail",) + FORMER_COPIES:
             assert not defines_function(name, text), f"{source} defines {name}"
         for name in SHARED_TYPES + ("Layer",):
             assert not re.search(r"\bstruct " + name + r"\b[^;]*\{", text), f"{source} defines {name}"

@@ -13,7 +13,7 @@ rm -f libprev.so
 obj=$(mktemp -d)
 trap 'rm -rf "$obj"' EXIT
 for file in $files; do git -C "$root" show "$rev:buzzdetect_amd/csrc/$file" > "$obj/$file"; done
-cp bd_internal.h bd_device.h "$obj/"
+cp *.h "$obj/"
 pids=()
 for src in *.hip; do
   f=${src%.hip}
