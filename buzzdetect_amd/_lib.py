@@ -395,6 +395,31 @@ CLUSTER_PROTOTYPES = {
     "bd_cluster_stats_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
+CALLS_ABI_VERSION = 1
+CALLS_TILE = 1024
+CALLS_MAX_WINDOWS = 1 << 20
+CALLS_MAX_COLUMNS = 64
+CALLS_MAX_BINS = 1 << 20
+CALLS_EVENT_FIELDS = 5              # first, last, n_on, peak, kept
+
+
+class bd_calls_rule(C.Structure):
+    _fields_ = [("high", C.c_float), ("low", C.c_float), ("link", C.c_int32), ("min_extent", C.c_int32)]
+
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_calls.h
+CALLS_PROTOTYPES = {
+    "bd_calls_abi_version": (C.c_int, []),
+    "bd_calls_events": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_calls_events_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_calls_bins": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_calls_bins_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -429,7 +454,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
             + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ENSEMBLE_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
-            + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()):
+            + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -459,6 +484,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: search ABI version {lib.bd_search_abi_version()} != {SEARCH_ABI_VERSION}; rebuild")
     if lib.bd_cluster_abi_version() != CLUSTER_ABI_VERSION:
         raise RuntimeError(f"{path}: cluster ABI version {lib.bd_cluster_abi_version()} != {CLUSTER_ABI_VERSION}; rebuild")
+    if lib.bd_calls_abi_version() != CALLS_ABI_VERSION:
+        raise RuntimeError(f"{path}: calls ABI version {lib.bd_calls_abi_version()} != {CALLS_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

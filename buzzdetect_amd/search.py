@@ -314,9 +314,10 @@ class _Index:
         return SearchResult(hits, list(messages), names)
 
 
-def _walk(dir_audio: str, engine, framehop_prop: float, chunklength: float, messages: List[str], feed) -> _Index:
+def _walk(dir_audio: str, engine, framehop_prop: float, chunklength: float, messages: List[str], feed, recording_done=None) -> _Index:
     """embed_annotated's loop: every recording analyze would take, launch set by launch set.  ``feed(parts, hop, step)`` runs
-    one set, hands its rows to a Searcher and returns (first id, windows per part); the rows are dropped before the next."""
+    one set, hands its rows to a Searcher and returns (first id, windows per part); the rows are dropped before the next.
+    ``recording_done(ident, chunk starts, windows per chunk)``, if given, is called after a recording's last set."""
     from .engine import hop_samples, patch_step
     framehop_s = FRAMELENGTH_S * framehop_prop
     hop, step = hop_samples(framehop_s), patch_step(framehop_s)
@@ -334,6 +335,8 @@ def _walk(dir_audio: str, engine, framehop_prop: float, chunklength: float, mess
             first_id = first if first_id is None else first_id
             all_counts += list(counts)
         index.add(ident, first_id, [c.start_s for c in chunks], all_counts)
+        if recording_done is not None:
+            recording_done(ident, [c.start_s for c in chunks], all_counts)
     return index
 
 
