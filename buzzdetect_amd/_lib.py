@@ -420,6 +420,26 @@ CALLS_PROTOTYPES = {
                                      C.c_void_p, C.c_void_p]),
 }
 
+EVAL_ABI_VERSION = 1
+EVAL_BINS = 16384
+EVAL_K_MIN = -8192
+EVAL_PLANES = 3                     # negatives by kf, positives by kf, labelled rows by kr
+EVAL_TAILS = 4                      # skipped, non-finite, below the range, above it
+EVAL_SLICE = 32768
+EVAL_MAX_WINDOWS = 1 << 24
+EVAL_MAX_COLUMNS = 2048
+EVAL_MAX_LABELS = 2048
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_eval.h
+EVAL_PROTOTYPES = {
+    "bd_eval_abi_version": (C.c_int, []),
+    "bd_eval_state_bytes": (C.c_int64, [C.c_int32]),
+    "bd_eval_accumulate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_eval_accumulate_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -454,7 +474,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     for name, (res, args) in list(PROTOTYPES.items()) + list(FLAC_PROTOTYPES.items()) + list(PCM_PROTOTYPES.items()) \
             + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ENSEMBLE_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
-            + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()):
+            + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()) \
+            + list(EVAL_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -486,6 +507,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: cluster ABI version {lib.bd_cluster_abi_version()} != {CLUSTER_ABI_VERSION}; rebuild")
     if lib.bd_calls_abi_version() != CALLS_ABI_VERSION:
         raise RuntimeError(f"{path}: calls ABI version {lib.bd_calls_abi_version()} != {CALLS_ABI_VERSION}; rebuild")
+    if lib.bd_eval_abi_version() != EVAL_ABI_VERSION:
+        raise RuntimeError(f"{path}: eval ABI version {lib.bd_eval_abi_version()} != {EVAL_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

@@ -314,19 +314,24 @@ class _Index:
         return SearchResult(hits, list(messages), names)
 
 
-def _walk(dir_audio: str, engine, framehop_prop: float, chunklength: float, messages: List[str], feed, recording_done=None) -> _Index:
+def _walk(dir_audio: str, engine, framehop_prop: float, chunklength: float, messages: List[str], feed, recording_done=None,
+          recording_starts=None, annotations=None, only_annotated: bool = False) -> _Index:
     """embed_annotated's loop: every recording analyze would take, launch set by launch set.  ``feed(parts, hop, step)`` runs
     one set, hands its rows to a Searcher and returns (first id, windows per part); the rows are dropped before the next.
-    ``recording_done(ident, chunk starts, windows per chunk)``, if given, is called after a recording's last set."""
+    ``recording_done(ident, chunk starts, windows per chunk)``, if given, is called after a recording's last set,
+    ``recording_starts(ident, chunk starts)`` before its first.  ``annotations`` / ``only_annotated``: as embed_annotated
+    takes them (recordings the annotations do not mention are left out; annotated ones that do not exist are reported)."""
     from .engine import hop_samples, patch_step
     framehop_s = FRAMELENGTH_S * framehop_prop
     hop, step = hop_samples(framehop_s), patch_step(framehop_s)
     chunklength = framing.round_chunklength(chunklength, FRAMELENGTH_S, DIGITS_TIME)
     index = _Index(framehop_s)
-    for path, ident in _recordings(dir_audio, {}, False, messages):
+    for path, ident in _recordings(dir_audio, {} if annotations is None else annotations, only_annotated, messages):
         chunks = _read_chunks(engine, path, ident, len(index.idents), chunklength, messages)
         if not chunks:
             continue
+        if recording_starts is not None:
+            recording_starts(ident, [c.start_s for c in chunks])
         parts = [c.pcm for c in chunks]
         windows = [engine.num_windows(int(p.numel()), hop, step) for p in parts]
         first_id, all_counts = None, []
