@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import yamnet_oracle as O
+from tests.dense_cases import stack_f64
 from tools import modelgen as G
 
 pytestmark = pytest.mark.gpu
@@ -18,25 +19,6 @@ HOP = 15360
 WINDOW_COUNTS = (1, 31, 1024, 1025, 4096)
 MODES = ("f32", "f16x3", "f16")
 LOGIT_GATE = 1e-4
-
-
-def stack_f64(emb, layers):
-    """The stack restated in float64 NumPy: y = act(x W + b) per layer."""
-    x = np.asarray(emb, dtype=np.float64)
-    for kernel, bias, act in layers:
-        x = x @ kernel.astype(np.float64) + bias.astype(np.float64)
-        if act == "relu":
-            x = np.maximum(x, 0.0)
-        elif act == "sigmoid":
-            x = 1.0 / (1.0 + np.exp(-x))
-        elif act == "tanh":
-            x = np.tanh(x)
-        elif act == "softmax":
-            e = np.exp(x - x.max(axis=1, keepdims=True))
-            x = e / e.sum(axis=1, keepdims=True)
-        else:
-            assert act == "linear"
-    return x
 
 
 @pytest.fixture(scope="module")
