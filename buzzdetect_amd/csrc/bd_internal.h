@@ -270,18 +270,10 @@ bool launch_tail_f32(const float* in, float* mid, float* pooled, int windows, co
                      int which);
 
 // ---- headmlp.hip ----
-// One Dense layer of an attached head stack (include/buzzdetect_head.h)
-struct DenseLayer {
-    int k, n;            // inputs, outputs
-    int act;             // BD_HEAD_*
-    const float* wfrag;  // the kernel in the f32 matrix instruction's B-fragment order, zero-padded (dense_pack_weights)
-    const float* bias;   // [n]
-};
+// A Dense kernel [k][n] in the f32 matrix instruction's B-fragment order, zero-padded to 32-column tiles and 32-k groups: what
+// dense_tile_walk (dense_device.h) reads in headset.hip, simsearch.hip and cluster.hip
 size_t dense_packed_floats(int k, int n);
 void dense_pack_weights(const float* kernel, int k, int n, float* dst);      // host: [k][n] -> fragment order
-// C[windows][ldc] (columns < n) = act(A[windows][lda] (columns < k) W + b); lda >= round_up(k, 32), A != C
-void launch_dense(const float* A, int lda, int windows, const DenseLayer& L, float* C, int ldc, hipStream_t stream);
-void launch_softmax_rows(const float* x, int ldx, float* y, int windows, int n, hipStream_t stream);  // x [windows][ldx] -> y [windows][n]
 
 }  // namespace bd
 
@@ -290,13 +282,15 @@ struct bd_headset_member;
 namespace bd {
 
 // ---- headset.hip ----
-// A set of heads behind one embedder pass (include/buzzdetect_headset.h).  Scratch per window: kHeadSetRegions rows of
+// The heads attached behind one embedder pass: a set (include/buzzdetect_headset.h), or a lone stack (include/buzzdetect_head.h),
+// which is a set of one member that the bd_headset_* calls do not see.  Scratch per window: kHeadSetRegions rows of
 // kHeadSetRow floats - two (ping, pong) take the hidden activations of every member, depth by depth, each layer in its own
 // 32-aligned column block; the third takes the last layers that stand in front of a softmax, packed like the logits.
 constexpr int kHeadSetRow = 2048;
 constexpr int kHeadSetRegions = 3;
 struct HeadSet {
-    int members = 0, outputs = 0;
+    bool lone = false;                       // bd_head_attach's stack: one member, never fused, members stays 0
+    int members = 0, outputs = 0;            // outputs: the row of the logits (or of the ensemble's wide region)
     std::vector<int> first, count;           // per member: its columns of the logits
     std::vector<int> last_act;               // per member: the activation of its last layer (BD_HEAD_*)
     char* dev = nullptr;                     // one allocation: packed kernels, biases, descriptors, tile tables
@@ -314,7 +308,9 @@ struct HeadSet {
     int n_fused = 0;
 };
 // Checks the limits, then uploads (synchronous).  BD_OK, or BD_EINVAL / BD_EHIP with *err set; *out is written on success only.
-int headset_build(const bd_headset_member* members, int n_members, HeadSet* out, std::string* err);
+// lone: the one member is bd_head_attach's stack - it takes the stack route whatever its shape (the fused route sums in another
+// order) and the messages name bd_head_attach.
+int headset_build(const bd_headset_member* members, int n_members, bool lone, HeadSet* out, std::string* err);
 void headset_free(HeadSet* set);
 // scratch = [kHeadSetRegions][windows][kHeadSetRow]
 void launch_dense_set(const HeadSet& set, int depth, const float* pooled, float* scratch, float* logits, int windows,

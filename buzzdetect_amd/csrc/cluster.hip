@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void cluster_assign_kernel(const float* _
 #pragma unroll 1
     for (int tc = 0; tc < tiles; ++tc) {
         const float4* bp = Cf + (size_t)tc * n_super * 64 + lane;
-        // (n_super is an argument, as in headmlp.hip: known at compile time, the walk unrolls whole and spills)
+        // (n_super is an argument, as in headset.hip: known at compile time, the walk unrolls whole and spills)
         const dense_v16f acc = dense_tile_walk(ap, bp, BD_CLUSTER_DIM, n_super, half);
         const int col = 32 * tc + (lane & 31);
         if (col < K) {                                    // a padded column never enters: it stays (+INFINITY, j >= K) at most

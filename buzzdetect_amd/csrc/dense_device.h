@@ -1,7 +1,6 @@
-// Device code shared by the dense-stack head (headmlp.hip: one stack per engine) and the set of heads (headset.hip: many
-// stacks behind one embedder pass): the walk of one wave over K for its 32 x 32 tile of C, the activation, and the order of a
-// softmax row.  Both files produce an output element through exactly this code, which is what makes a member of a set give the
-// bits of the same stack attached alone.
+// Device code of the attached heads (headset.hip: a lone stack or many stacks behind one embedder pass): the walk of one wave
+// over K for its 32 x 32 tile of C, the activation, and the order of a softmax row.  simsearch.hip and cluster.hip take the walk
+// for their own products.
 #pragma once
 
 #include <hip/hip_runtime.h>

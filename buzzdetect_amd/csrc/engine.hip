@@ -176,7 +176,6 @@ int bd_destroy(bd_handle h) {
     if (h->d_range_flag) (void)hipFree(h->d_range_flag);
     bd::resample_release(h);
     if (h->d_amax) (void)hipFree(h->d_amax);
-    if (h->d_stack) (void)hipFree(h->d_stack);
     bd::headset_free(&h->set);
     bd::ensemble_free(&h->ens);
     delete h;

@@ -99,39 +99,16 @@ void pointwise(Group& g, int l) {
     g.launch(3 + 2 * l, [&] { bd::launch_pointwise(g.b, g.a, (int64_t)g.gw * L.h_out * L.w_out, L, g.stream); });
 }
 
-// Floats per window an attached stack's hidden activations take: two rows (ping, pong) of the widest padded layer
-constexpr int kStackRow = (BD_HEAD_MAX_WIDTH + 31) / 32 * 32;
-static_assert(BD_EMBEDDING_SIZE + 2 * kStackRow <= kFloatsB, "pooled embeddings + hidden activations of a stack fit either buffer");
-
-// The attached dense stack (headmlp.hip) on pooled = [gw][1024]: one launch per layer, hidden activations ping-pong through
-// `scratch` (2 * kStackRow floats per window, free at this point of the pass), the last layer lands in the logits - or, in front
-// of a softmax, in scratch too, and the row pass writes the logits (every launch stays idempotent); all in slot 28
-int stack_head(Group& g, const float* pooled, float* scratch) {
-    const std::vector<bd::DenseLayer>& st = g.e->stack;
-    const float* in = pooled;
-    int ld_in = BD_EMBEDDING_SIZE;
-    for (size_t i = 0; i < st.size(); ++i) {
-        const bool last = i + 1 == st.size() && st[i].act != BD_HEAD_SOFTMAX;
-        float* out = last ? g.logits : scratch + (i & 1) * (size_t)g.gw * kStackRow;
-        const int ld_out = last ? st[i].n : (st[i].n + 31) / 32 * 32;
-        g.launch(28, [&] { bd::launch_dense(in, ld_in, g.gw, st[i], out, ld_out, g.stream); });
-        in = out;
-        ld_in = ld_out;
-    }
-    if (st.back().act == BD_HEAD_SOFTMAX)
-        g.launch(28, [&] { bd::launch_softmax_rows(in, ld_in, g.logits, g.gw, st.back().n, g.stream); });
-    return BD_OK;
-}
-
 static_assert(BD_EMBEDDING_SIZE + (bd::kHeadSetRegions + 1) * bd::kHeadSetRow <= kFloatsB,
               "pooled embeddings + the scratch of a set of heads + the members' columns under an ensemble fit either buffer");
 static_assert(bd::kEnsembleRegion == bd::kHeadSetRegions && BD_HEAD_MAX_WIDTH <= bd::kHeadSetRow, "the wide row of an ensemble is the region behind the set's own");
 
-// The attached set of heads (headset.hip) on pooled = [gw][1024]: one launch per depth of its deepest stack, one softmax row
-// pass, one launch for the members of the fused kind - whatever the number of members; scratch = kHeadSetRegions *
-// kHeadSetRow floats per window.  With an ensemble over the set (ensemble.hip) the members' columns go to a fourth region, rows
-// of set.outputs floats packed as the logits would be, and one more launch writes the logits from it.  All in slot 28
-int set_head(Group& g, const float* pooled, float* scratch) {
+// The attached heads (headset.hip: a lone stack or a set) on pooled = [gw][1024]: one launch per depth of the deepest stack, one
+// softmax row pass, one launch for the members of the fused kind - whatever the number of members; scratch = kHeadSetRegions *
+// kHeadSetRow floats per window, free at this point of the pass.  With an ensemble over the set (ensemble.hip) the members'
+// columns go to a fourth region, rows of set.outputs floats packed as the logits would be, and one more launch writes the logits
+// from it.  All in slot 28
+int attached_head(Group& g, const float* pooled, float* scratch) {
     const bd::HeadSet& set = g.e->set;
     const bd::Ensemble& ens = g.e->ens;
     float* wide = ens.n_outputs ? scratch + bd::kEnsembleRegion * (size_t)g.gw * bd::kHeadSetRow : g.logits;
@@ -146,8 +123,7 @@ int set_head(Group& g, const float* pooled, float* scratch) {
 // The dense head on the embeddings a tail kernel pooled (into the embeddings or b: a is free by now)
 int head(Group& g, const float* pooled) {
     if (!g.logits) return BD_OK;
-    if (g.e->set.members) return set_head(g, pooled, g.a);
-    if (!g.e->stack.empty()) return stack_head(g, pooled, g.a);
+    if (g.e->set.dev) return attached_head(g, pooled, g.a);
     g.launch(28, [&] { bd::launch_head(pooled, g.gw, g.e->head_wt, g.e->head_b, g.e->n_classes, g.logits, g.stream); });
     return BD_OK;
 }
@@ -172,13 +148,12 @@ int walk_layers(Group& g, int from, bool dw_done, int stop_stage) {
         pointwise(g, l);
         dw_done = false;
     }
-    if (stop_stage < 0 && (!g.e->stack.empty() || g.e->set.members) && g.logits) {
-        // pool alone (a -> the embeddings, or the front of b: the last 1x1 convolution has read b), then the stack (or the set
-        // of heads) behind it
+    if (stop_stage < 0 && g.e->set.dev && g.logits) {
+        // pool alone (a -> the embeddings, or the front of b: the last 1x1 convolution has read b), then the attached heads
+        // behind it
         float* const pooled = g.emb ? g.emb : g.b;
         g.launch(28, [&] { bd::launch_pool_head(g.a, g.gw, nullptr, nullptr, 0, pooled, nullptr, g.stream); });
-        if (g.e->set.members) return set_head(g, pooled, g.b + (size_t)g.gw * BD_EMBEDDING_SIZE);
-        return stack_head(g, pooled, g.b + (size_t)g.gw * BD_EMBEDDING_SIZE);
+        return attached_head(g, pooled, g.b + (size_t)g.gw * BD_EMBEDDING_SIZE);
     }
     if (stop_stage < 0)
         g.launch(28, [&] {

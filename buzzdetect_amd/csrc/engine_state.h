@@ -4,7 +4,8 @@
 //   weights_fold.hip    BatchNorm folding and the layout of the weight pool (no HIP runtime call)
 //   engine_pass.hip     the launch plan of a batch of chunks, calibration, workspace layout
 //   resample_host.hip   filter design and the resampler's filter caches
-//   headmlp.hip / headset.hip / ensemble.hip    attach and query exports of the three head kinds, beside their kernels
+//   headmlp.hip / headset.hip / ensemble.hip    attach and query exports of the three head kinds; a lone stack and a set run
+//                       on headset.hip's kernels
 #pragma once
 
 #include <cmath>
@@ -122,10 +123,8 @@ struct bd_engine {
     bd::SepLayer sep[13];
     const float* head_wt = nullptr;   // [n_classes][1024]
     const float* head_b = nullptr;
-    // a dense stack in place of that head (bd_head_attach): n_classes is then its last width
-    std::vector<bd::DenseLayer> stack;
-    float* d_stack = nullptr;         // one allocation for the stack's packed kernels and biases
-    // or a set of heads (bd_headset_attach, headset.hip): n_classes is then the sum of the members' last widths
+    // heads attached in place of that head (headset.hip; set.dev != nullptr): a lone dense stack (bd_head_attach, set.lone) or
+    // a set of heads (bd_headset_attach) - n_classes is then the sum of the members' last widths
     bd::HeadSet set;
     // and outputs over that set's members (bd_ensemble_attach, ensemble.hip): n_classes is then the sum of the outputs' widths
     bd::Ensemble ens;

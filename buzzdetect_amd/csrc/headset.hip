@@ -1,19 +1,20 @@
-// A set of classifier heads behind one embedder pass (include/buzzdetect_headset.h): M members, each a stack bd_head_attach
-// would take, whose outputs land side by side in the logits.  Launches per pass do not grow with M:
+// The heads attached to an engine (include/buzzdetect_headset.h, include/buzzdetect_head.h): M members, each a stack of Dense
+// layers, whose outputs land side by side in the logits.  A lone stack (bd_head_attach, headmlp.hip) is a set of one member that
+// never takes the fused route.  Launches per pass do not grow with M:
 //
 //   dense_set_kernel    one launch per DEPTH: the layer at that depth of every stack-route member.  blockIdx.y walks a tile
 //                       table built at attach time: every 64-column workgroup tile of every such layer names its layer
 //                       descriptor (where A is, K, the packed fragments, the bias, N, the activation, where C goes).  A wave
-//                       then does exactly what dense_kernel's wave does for that layer alone (dense_device.h: the walk over K
-//                       and the epilogue are the same code), so an output has the bits the lone stack gives it.
-//   softmax_set_kernel  one launch for every member that ends in a softmax, in softmax_rows_kernel's order (dense_device.h).
+//                       owns one 32 x 32 tile of C and walks K alone (dense_device.h), so an output depends on its row of A, its
+//                       column of W and the k order only: a member has the bits of the same stack attached alone.
+//   softmax_set_kernel  one launch for every member that ends in a softmax, one wave per row (dense_device.h: softmax_row).
 //   head_set_kernel     one launch for the members of the fused kind (one linear layer of at most BD_MAX_CLASSES outputs): their
 //                       classes are concatenated and cut into groups of at most 64, grid (window, group); a class is computed
 //                       as pool_head_kernel<1> (cnn.hip) computes it - per thread fmaf(s.x, w.x, fmaf(s.y, w.y, fmaf(s.z, w.z,
 //                       s.w * w.w))) over its float4 of the embedding, an xor butterfly over the wave, ((p0 + p1) + (p2 + p3)) +
 //                       bias over the four waves - and depends on no other class, so the grouping changes nothing.
 //
-// Scratch (bd_internal.h: kHeadSetRegions rows of kHeadSetRow floats per window, inside the workspace a stack already uses):
+// Scratch (bd_internal.h: kHeadSetRegions rows of kHeadSetRow floats per window, inside the workspace of the pass):
 // depth d reads region (d - 1) & 1 and writes region d & 1, every layer in a 32-aligned column block of its own (A's 16-byte
 // loads reach round_up(K, 32) columns; those at k >= K are replaced by zero, never used); a last layer in front of a softmax
 // writes region 2, packed, where no later depth writes; every other last layer writes its member's columns of the logits.
@@ -116,14 +117,43 @@ __global__ __launch_bounds__(256) void head_set_kernel(const float* __restrict__
 inline int pad32(int v) { return (v + 31) / 32 * 32; }
 inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
-bool fused_route(const bd_headset_member& m) {
-    return m.n_layers == 1 && m.layers[0].activation == BD_HEAD_LINEAR && m.layers[0].n_out <= BD_MAX_CLASSES;
+bool fused_route(const bd_headset_member& m, bool lone) {
+    return !lone && m.n_layers == 1 && m.layers[0].activation == BD_HEAD_LINEAR && m.layers[0].n_out <= BD_MAX_CLASSES;
+}
+
+// The shape checks on one stack's layers; `stack` / `layer` open the messages ("bd_head_attach: " / "bd_head_attach: layer ")
+int check_stack(const bd_head_layer* layers, int n_layers, const std::string& stack, const std::string& layer, std::string* err) {
+    if (n_layers < 1 || n_layers > BD_HEAD_MAX_LAYERS) {
+        *err = stack + "a stack has 1.." + std::to_string(BD_HEAD_MAX_LAYERS) + " layers, not " + std::to_string(n_layers);
+        return BD_EINVAL;
+    }
+    int width = BD_EMBEDDING_SIZE;
+    for (int i = 0; i < n_layers; ++i) {
+        const bd_head_layer& L = layers[i];
+        const std::string lw = layer + std::to_string(i);
+        if (!L.kernel) { *err = lw + " has no kernel"; return BD_EINVAL; }
+        if (L.n_out < 1 || L.n_out > BD_HEAD_MAX_WIDTH) {
+            *err = lw + ": width " + std::to_string(L.n_out) + " outside 1.." + std::to_string(BD_HEAD_MAX_WIDTH);
+            return BD_EINVAL;
+        }
+        if (L.n_in != width) {
+            *err = lw + " takes " + std::to_string(L.n_in) + " inputs, the layer before it gives " + std::to_string(width);
+            return BD_EINVAL;
+        }
+        if (L.activation < BD_HEAD_LINEAR || L.activation > BD_HEAD_SOFTMAX) {
+            *err = lw + ": unknown activation " + std::to_string(L.activation);
+            return BD_EINVAL;
+        }
+        if (L.activation == BD_HEAD_SOFTMAX && i + 1 != n_layers) { *err = lw + ": softmax on a hidden layer"; return BD_EINVAL; }
+        width = L.n_out;
+    }
+    return BD_OK;
 }
 
 }  // namespace
 
-int headset_build(const bd_headset_member* members, int n_members, HeadSet* out, std::string* err) {
-    const std::string fn = "bd_headset_attach: ";
+int headset_build(const bd_headset_member* members, int n_members, bool lone, HeadSet* out, std::string* err) {
+    const std::string fn = lone ? "bd_head_attach: " : "bd_headset_attach: ";
     if (n_members < 1 || n_members > BD_HEADSET_MAX_MEMBERS) {
         *err = fn + "a set has 1.." + std::to_string(BD_HEADSET_MAX_MEMBERS) + " members, not " + std::to_string(n_members);
         return BD_EINVAL;
@@ -134,32 +164,11 @@ int headset_build(const bd_headset_member* members, int n_members, HeadSet* out,
         const bd_headset_member& M = members[m];
         const std::string who = fn + "member " + std::to_string(m);
         if (!M.layers) { *err = who + " has no layers"; return BD_EINVAL; }
-        if (M.n_layers < 1 || M.n_layers > BD_HEAD_MAX_LAYERS) {
-            *err = who + ": a stack has 1.." + std::to_string(BD_HEAD_MAX_LAYERS) + " layers, not " + std::to_string(M.n_layers);
-            return BD_EINVAL;
-        }
-        int width = BD_EMBEDDING_SIZE;
-        for (int i = 0; i < M.n_layers; ++i) {
-            const bd_head_layer& L = M.layers[i];
-            const std::string lw = who + " layer " + std::to_string(i);
-            if (!L.kernel) { *err = lw + " has no kernel"; return BD_EINVAL; }
-            if (L.n_out < 1 || L.n_out > BD_HEAD_MAX_WIDTH) {
-                *err = lw + ": width " + std::to_string(L.n_out) + " outside 1.." + std::to_string(BD_HEAD_MAX_WIDTH);
-                return BD_EINVAL;
-            }
-            if (L.n_in != width) {
-                *err = lw + " takes " + std::to_string(L.n_in) + " inputs, the layer before it gives " + std::to_string(width);
-                return BD_EINVAL;
-            }
-            if (L.activation < BD_HEAD_LINEAR || L.activation > BD_HEAD_SOFTMAX) {
-                *err = lw + ": unknown activation " + std::to_string(L.activation);
-                return BD_EINVAL;
-            }
-            if (L.activation == BD_HEAD_SOFTMAX && i + 1 != M.n_layers) { *err = lw + ": softmax on a hidden layer"; return BD_EINVAL; }
-            width = L.n_out;
-        }
-        outputs += width;
-        if (!fused_route(M) && M.n_layers > max_depth) max_depth = M.n_layers;
+        const int rc = lone ? check_stack(M.layers, M.n_layers, fn, fn + "layer ", err)
+                            : check_stack(M.layers, M.n_layers, who + ": ", who + " layer ", err);
+        if (rc != BD_OK) return rc;
+        outputs += M.layers[M.n_layers - 1].n_out;
+        if (!fused_route(M, lone) && M.n_layers > max_depth) max_depth = M.n_layers;
     }
     if (outputs > BD_HEAD_MAX_WIDTH) {
         *err = fn + "the members' outputs sum to " + std::to_string(outputs) + ", more than " + std::to_string(BD_HEAD_MAX_WIDTH);
@@ -169,7 +178,7 @@ int headset_build(const bd_headset_member* members, int n_members, HeadSet* out,
         long long sum = 0;
         for (int m = 0; m < n_members; ++m) {
             const bd_headset_member& M = members[m];
-            if (fused_route(M) || d >= M.n_layers) continue;
+            if (fused_route(M, lone) || d >= M.n_layers) continue;
             if (d + 1 < M.n_layers || M.layers[d].activation == BD_HEAD_SOFTMAX) sum += pad32(M.layers[d].n_out);
         }
         if (sum > kHeadSetRow) {
@@ -181,7 +190,8 @@ int headset_build(const bd_headset_member* members, int n_members, HeadSet* out,
 
     // ---- layout: parameters (floats), then the descriptors ----
     HeadSet set;
-    set.members = n_members;
+    set.lone = lone;
+    set.members = lone ? 0 : n_members;
     set.outputs = (int)outputs;
     std::vector<float> params;
     std::vector<std::vector<SetLayer>> layers(max_depth);
@@ -197,7 +207,7 @@ int headset_build(const bd_headset_member* members, int n_members, HeadSet* out,
         set.first.push_back(col);
         set.count.push_back(n_last);
         set.last_act.push_back(M.layers[M.n_layers - 1].activation);
-        if (fused_route(M)) {
+        if (fused_route(M, lone)) {
             const bd_head_layer& L = M.layers[0];
             for (int c = 0; c < L.n_out; ++c) {             // [1024][n] -> [class][1024], as bd_create keeps its head
                 for (int k = 0; k < BD_EMBEDDING_SIZE; ++k) fused_wt.push_back(L.kernel[(size_t)k * L.n_out + c]);
@@ -326,7 +336,7 @@ int bd_headset_members(bd_handle h) {
 
 int bd_headset_outputs(bd_handle h) {
     if (!h) return fail(BD_EINVAL, "bd_headset_outputs: null handle");
-    return h->set.outputs;
+    return h->set.lone ? 0 : h->set.outputs;
 }
 
 int bd_headset_columns(bd_handle h, int32_t member, int32_t* first, int32_t* count) {
@@ -342,13 +352,13 @@ int bd_headset_columns(bd_handle h, int32_t member, int32_t* first, int32_t* cou
 int bd_headset_attach(bd_handle h, const bd_headset_member* members, int32_t n_members) {
     if (!h || !members) return fail(BD_EINVAL, "bd_headset_attach: null argument");
     if (h->set.members) return fail(BD_EINVAL, "bd_headset_attach: the engine already has a set of heads");
-    if (!h->stack.empty()) return fail(BD_EINVAL, "bd_headset_attach: the engine already has a stack (bd_head_attach)");
+    if (h->set.lone) return fail(BD_EINVAL, "bd_headset_attach: the engine already has a stack (bd_head_attach)");
     if (h->n_classes != 0)
         return fail(BD_EINVAL, "bd_headset_attach: the engine already has a head (create it with n_classes == 0)");
     BD_HIP(hipSetDevice(h->device));
     std::string err;
     bd::HeadSet set;
-    const int rc = bd::headset_build(members, n_members, &set, &err);
+    const int rc = bd::headset_build(members, n_members, false, &set, &err);
     if (rc != BD_OK) return fail(rc, err);
     h->set = std::move(set);
     h->n_classes = h->set.outputs;

@@ -26,7 +26,7 @@ static_assert(kSliceRows % 32 == 0, "a slice is whole 32-row steps of the matrix
 
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float act_fwd(float x, int act) {       // headmlp.hip's head_act
+__device__ __forceinline__ float act_fwd(float x, int act) {       // dense_device.h's head_act
     if (act == BD_HEAD_RELU) return fmaxf(x, 0.0f);
     if (act == BD_HEAD_SIGMOID) return 1.0f / (1.0f + expf(-x));
     if (act == BD_HEAD_TANH) return tanhf(x);

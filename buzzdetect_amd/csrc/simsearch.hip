@@ -2,8 +2,8 @@
 // they lie, and a running top-k per query, so that no [W][1024] row goes back to the host.
 //
 //   search_norms_kernel    a wave per row: 64 chains of 16 fused multiply-adds, one butterfly (simsearch_device.h).
-//   search_scores_kernel   S = E Q^T on v_mfma_f32_32x32x2_f32 by dense_tile_walk (dense_device.h: the walk of headmlp.hip and
-//                          headset.hip): a wave owns a 32 x 32 tile and walks K = 1024 alone, E straight from global memory,
+//   search_scores_kernel   S = E Q^T on v_mfma_f32_32x32x2_f32 by dense_tile_walk (dense_device.h: the walk of the dense
+//                          heads, headset.hip): a wave owns a 32 x 32 tile and walks K = 1024 alone, E straight from global memory,
 //                          the queries from the fragment order bd_search_pack_queries wrote.  A workgroup is 2 x 2 waves.  The
 //                          epilogue divides by the root of the row's squared norm (cosine) and stores by two element strides.
 //   search_update_kernel   a workgroup per query.  LDS holds 2048 keys: the state in [0, k), survivors parked behind it.  The

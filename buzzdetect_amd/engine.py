@@ -318,10 +318,11 @@ class HipEngine:
         self._pinned_events: list = [None] * 4
         self._pinned_next = 0
 
-    def _attach_stack(self, layers) -> None:
-        """``bd_head_attach``: the Dense stack in place of the fused head (the library copies the arrays)."""
+    @staticmethod
+    def _head_layers(layers, keep: list):
+        """The ``bd_head_layer`` array of one stack's (kernel, bias, activation) triples; the float32 arrays it points to go
+        to ``keep``."""
         arr = (_lib.bd_head_layer * len(layers))()
-        keep = []
         for i, (kernel, bias, activation) in enumerate(layers):
             k = np.ascontiguousarray(kernel, dtype=np.float32)
             b = np.ascontiguousarray(bias, dtype=np.float32)
@@ -330,6 +331,12 @@ class HipEngine:
             arr[i].bias = b.ctypes.data_as(C.POINTER(C.c_float))
             arr[i].n_in, arr[i].n_out = k.shape
             arr[i].activation = _lib.HEAD_ACTIVATIONS[activation]
+        return arr
+
+    def _attach_stack(self, layers) -> None:
+        """``bd_head_attach``: the Dense stack in place of the fused head (the library copies the arrays)."""
+        keep = []
+        arr = self._head_layers(layers, keep)
         _lib.check(self._lib.bd_head_attach(self._handle, arr, len(layers)))
         if self._lib.bd_head_outputs(self._handle) != self.n_classes:
             raise RuntimeError("bd_head_attach: the attached stack's width differs from the number of classes")
@@ -373,15 +380,7 @@ class HipEngine:
         arr = (_lib.bd_headset_member * len(heads))()
         keep = []
         for m, head in enumerate(heads.values()):
-            layers = (_lib.bd_head_layer * len(head.layers))()
-            for i, (kernel, bias, activation) in enumerate(head.layers):
-                k = np.ascontiguousarray(kernel, dtype=np.float32)
-                b = np.ascontiguousarray(bias, dtype=np.float32)
-                keep += [k, b]
-                layers[i].kernel = k.ctypes.data_as(C.POINTER(C.c_float))
-                layers[i].bias = b.ctypes.data_as(C.POINTER(C.c_float))
-                layers[i].n_in, layers[i].n_out = k.shape
-                layers[i].activation = _lib.HEAD_ACTIVATIONS[activation]
+            layers = self._head_layers(head.layers, keep)
             keep.append(layers)
             arr[m].layers = layers
             arr[m].n_layers = len(head.layers)

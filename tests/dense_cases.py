@@ -199,7 +199,7 @@ WIDE = [
     stack("out2048", [2048], ["sigmoid"], "N = 2048 on the last layer: bd_head_outputs at BD_HEAD_MAX_WIDTH"),
     stack("out2047", [2047], ["tanh"], "N = 2047 on the last layer: the last tile one column short"),
     stack("hid2048", [2048, 2048, 13], ["tanh", "sigmoid", "linear"],
-          "K = 2048 and hidden N = 2048 twice: tanh and sigmoid on a 2048-wide hidden layer, rows kStackRow floats apart"),
+          "K = 2048 and hidden N = 2048 twice: tanh and sigmoid on a 2048-wide hidden layer, rows kHeadSetRow floats apart"),
     stack("hid2047", [2047, 65], ["sigmoid", "linear"],
           "K = 2047: the last 16-byte load of a row straddles a written and a never-written column"),
     stack("sm2048", [64, 2048], ["relu", "softmax"], "softmax of length 2048: 32 rounds per lane, region 2 of a set full"),

@@ -139,6 +139,30 @@ def test_the_one_kernel_per_op_plan_gives_the_default_plans_bits(tmp_path_factor
         eng.close()
 
 
+def test_a_narrow_linear_stack_has_the_bits_of_its_columns_in_a_wide_one(audio):
+    """bd_head_attach itself on two engines made without a head: one linear layer 1024 -> 13, and one 1024 -> 65 whose first 13
+    columns are that layer.  An output depends only on its row of A, its column of W and the k order of the matrix-core walk, so
+    the 13 columns are byte-equal - unless a stack of at most 64 linear outputs ever ran as a fused-route member, whose sum
+    has another order."""
+    from buzzdetect_amd.engine import HipEngine
+    (kernel, bias, _), = G.glorot_layers([65], ["linear"], seed=23)
+    stacks = {13: [(np.ascontiguousarray(kernel[:, :13]), bias[:13].copy(), "linear")], 65: [(kernel, bias, "linear")]}
+    x = audio[: HOP * 65 + 240]
+    rows = {}
+    for n, layers in stacks.items():
+        eng = HipEngine(modelname=None)
+        try:
+            eng.n_classes = n                            # what _attach_stack holds bd_head_outputs to
+            eng._attach_stack(layers)
+            assert eng._lib.bd_head_outputs(eng._handle) == n and eng._lib.bd_headset_members(eng._handle) == 0
+            rows[n] = eng.predict(x, 0.96).numpy().copy()
+        finally:
+            eng.close()
+    assert rows[13].shape == (65, 13) and rows[65].shape == (65, 65) and rows[13].dtype == np.float32
+    assert np.abs(rows[13]).max() > 0.0
+    assert rows[13].tobytes() == np.ascontiguousarray(rows[65][:, :13]).tobytes()
+
+
 def write_wav(path, x, rate=16000):
     with wave.open(str(path), "wb") as w:
         w.setnchannels(1)
