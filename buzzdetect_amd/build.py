@@ -28,7 +28,7 @@ FILE_FLAGS = {
     "sepchipf32.hip": ("-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"),
     "sepmidf32.hip": ("-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"),
 }
-HEADERS = ("bd_internal.h", "bd_error.h", "engine_state.h", "bd_device.h", "headtrain_device.h", "headtrain_host.h", "dense_device.h", "ensemble_device.h", "simsearch_device.h", "cluster_device.h", "calls_device.h", "evalsweep_device.h", os.path.join("..", "..", "include", "buzzdetect_hip.h"),
+HEADERS = ("bd_internal.h", "bd_error.h", "engine_state.h", "bd_device.h", "headtrain_device.h", "headtrain_host.h", "headtrain_stack.h", "dense_device.h", "ensemble_device.h", "simsearch_device.h", "cluster_device.h", "calls_device.h", "evalsweep_device.h", os.path.join("..", "..", "include", "buzzdetect_hip.h"),
            os.path.join("..", "..", "include", "buzzdetect_flac.h"), os.path.join("..", "..", "include", "buzzdetect_pcm.h"),
            os.path.join("..", "..", "include", "buzzdetect_head.h"),
            os.path.join("..", "..", "include", "buzzdetect_headset.h"),

@@ -103,7 +103,8 @@ __global__ __launch_bounds__(512) void bank_step_kernel(const float* __restrict_
 
 // grid (a.count): member a.first + blockIdx.x's batch loss to out[member]; its running sum moves unless the member is frozen
 __global__ __launch_bounds__(256) void bank_loss_sum_kernel(const float* __restrict__ row_loss, int B, int max_batch, double scale,
-                                                             float* __restrict__ out, double* __restrict__ acc, Members a) {
+                                                             float* __restrict__ out, double* __restrict__ acc,
+                                                             Members<kMembersPerLaunch> a) {
     __shared__ double part[256];
     const int member = a.first + blockIdx.x;
     loss_sum_block(row_loss + (size_t)member * max_batch, B, scale, out ? out + member : nullptr,
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256) void bank_loss_sum_kernel(const float* __restr
 // grid (ceil((1024 C + C) / 256), a.count): element i = k C + c of member a.first + blockIdx.y's [W | b]
 __global__ __launch_bounds__(256) void bank_apply_kernel(const float* __restrict__ ws, int slices, Shape s, float* __restrict__ grad,
                                                           float* __restrict__ P, float* __restrict__ m, float* __restrict__ v,
-                                                          int kind, float b1, float b2, float eps, Members a) {
+                                                          int kind, float b1, float b2, float eps, Members<kMembersPerLaunch> a) {
     const int j = blockIdx.y, member = a.first + j;
     if (a.frozen[j]) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -278,7 +279,7 @@ int bd_bank_step(bd_bank b, const float* X, int64_t ldx, const int32_t* rows, co
                            b->loss, targets, row_w, ldw, inv, b->row_loss, b->ws);
     const int n = (bd::kIn + 1) * s.C;
     for (int first = 0; first < s.M; first += bd::kMembersPerLaunch) {
-        const bd::Members a = b->members.launch_args(b->opt, first);
+        const bd::Members<bd::kMembersPerLaunch> a = b->members.launch_args(b->opt, first);
         hipLaunchKernelGGL(bd::bank_loss_sum_kernel, dim3(a.count), dim3(256), 0, stream, b->row_loss, B, s.max_batch,
                            bd::loss_scale(b->loss, B, s.C), (float*)nullptr, b->acc, a);
         hipLaunchKernelGGL(bd::bank_apply_kernel, dim3((n + 255) / 256, a.count), dim3(256), 0, stream, b->ws, slices, s, b->grad, b->p,
@@ -308,7 +309,7 @@ int bd_bank_loss(bd_bank b, const float* X, int64_t ldx, const int32_t* rows, co
         hipLaunchKernelGGL(bd::bank_loss_rows_kernel<false>, dim3((B + 3) / 4, s.M), dim3(256), 0, stream, b->z, b->g, B, s, b->loss,
                            targets, row_w, ldw, inv, b->row_loss);
     for (int first = 0; first < s.M; first += bd::kMembersPerLaunch) {
-        const bd::Members a = bd::members_from(s.M, first);
+        const bd::Members<bd::kMembersPerLaunch> a = bd::members_from(s.M, first);
         hipLaunchKernelGGL(bd::bank_loss_sum_kernel, dim3(a.count), dim3(256), 0, stream, b->row_loss, B, s.max_batch,
                            bd::loss_scale(b->loss, B, s.C), loss_dev, (double*)nullptr, a);
     }

@@ -1,12 +1,15 @@
 // The classifier-head trainer (include/buzzdetect_train.h): forward, loss, backward and update of a Dense stack on
 // embeddings, in exact float32 on v_mfma_f32_32x32x2_f32.
 //
-// This file: the trainer's kernels, its pool (a Dense stack's pieces as headtrain_host.h lays them out, then the workspace, the
-// rows' losses and the running loss) and the launches of its entry points.  The device routines - mma_chain and the tiles
-// built on it, loss_row, the partials' sum and the update - live in headtrain_device.h, and the host side the three training
-// families share - the checks, the trainer's rate, decay, snapshot flag and step count (a MemberState of one member), the
-// bias-corrected Adam rate, the stack's layout, the running loss and the workspace's test hooks - in headtrain_host.h;
-// headbank.hip and stackbank.hip include both too.  The three matrix products differ in where a lane finds its operands:
+// This file: the trainer's handle, its pool (a Dense stack's pieces as headtrain_host.h lays them out, then the workspace, the
+// rows' losses and the running loss), its entry points and the one kernel that is the trainer's alone, fused_step_kernel.
+// The layer-by-layer route - forward, rows' losses and their sum, weight gradient, input gradient, update: six kernels and
+// their launches - is headtrain_stack.h's, shared with stackbank.hip: the trainer hands it its pool as a run of one member
+// (run_of), so the lone trainer is a stack bank of one.  The device routines - mma_chain and the tiles built on it, loss_row,
+// the partials' sum and the update - live in headtrain_device.h, and the host side the three training families share - the
+// checks, the trainer's rate, decay, snapshot flag and step count (a MemberState of one member), the bias-corrected Adam
+// rate, the stack's layout, the running loss and the workspace's test hooks - in headtrain_host.h; headbank.hip and
+// stackbank.hip include both too.  The three matrix products differ in where a lane finds its operands:
 //   forward  Y = act(A W + b)      reduce over n_in    A: 16 bytes of a row (row rows[r] of X for layer 0)   B: W[k][col]
 //   dA       G' = (G W^T) * act'   reduce over n_out   A: 16 bytes of a row of G                             B: W[col][k]
 //   dW       P_s = A^T G           reduce over the rows of slice s   A: A[row][col]                          B: G[row][col]
@@ -14,68 +17,24 @@
 //
 // Order of sums (the determinism contract): an output element is one chain of fused multiply-adds in ascending k.  dW reduces
 // over the batch: slice s is rows [256 s, 256 s + 256) - kSliceRows, a constant - its partial goes to workspace
-// [slice][n_in n_out + n_out], and apply_kernel adds the partials in ascending s before the optimizer's update.  Row losses go
+// [slice][n_in n_out + n_out], and stack_apply_kernel adds the partials in ascending s before the optimizer's update.  Row losses go
 // to a buffer and one workgroup adds them in a fixed tree.  Nothing depends on the grid or the number of compute units.
 //
-// fused_step_kernel (one layer, n_out <= 64): a workgroup of eight waves owns a slice and calls the same three routines -
+// fused_step_kernel (one layer, n_out <= 64): a workgroup of eight waves owns a slice and calls the route's three routines -
 // logits of its 256 rows, their deltas, the slice's dW partial - so the partial's second walk over the slice's rows of X finds
 // them in the cache the first walk filled: X comes from HBM once per step.
 //
 // Row weights (bd_trainer_step_weighted): loss_row<true> reads w_r beside the row's target and uses scale_r = inv * w_r where
 // the plain pass uses inv, and stores w_r * loss_r; loss_row<false> is the plain pass, instruction for instruction.  The
 // weight is a kernel argument, the same for every lane: no lane leaves or branches apart in front of the fused kernel's
-// barriers.  Decoupled weight decay is apply_kernel's: p = p - (lr wd) p on a layer's kernel elements (never its bias), two
+// barriers.  Decoupled weight decay is stack_apply_kernel's: p = p - (lr wd) p on a layer's kernel elements (never its bias), two
 // roundings, before the optimizer's update is subtracted from p.
 #include "headtrain_device.h"
 #include "headtrain_host.h"
+#include "headtrain_stack.h"
 
 namespace bd {
 namespace {
-
-// ---- kernels ----
-
-__global__ __launch_bounds__(256) void forward_kernel(const float* __restrict__ A, int64_t lda, const int* __restrict__ rows, int B,
-                                                       int K, const float* __restrict__ P, int N, int act, float* __restrict__ Y,
-                                                       int ldy) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tr = 2 * blockIdx.x + (wave & 1), tc = 2 * blockIdx.y + (wave >> 1);
-    if (32 * tr >= B || 32 * tc >= N) return;           // (no barrier in this kernel)
-    forward_tile(A, lda, rows, B, K, P, N, act, Y, ldy, tr, tc, lane);
-}
-
-__global__ __launch_bounds__(256) void input_grad_kernel(const float* __restrict__ G, int ldg, int B, int K,
-                                                          const float* __restrict__ W, int N, const float* __restrict__ Yp, int act_p,
-                                                          float* __restrict__ Gp, int ldp) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tr = 2 * blockIdx.x + (wave & 1), tc = 2 * blockIdx.y + (wave >> 1);
-    if (32 * tr >= B || 32 * tc >= K) return;
-    input_grad_tile(G, ldg, B, K, W, N, Yp, act_p, Gp, ldp, tr, tc, lane);
-}
-
-// grid (ceil(tiles / 4), slices): a wave per 32 x 32 tile of a slice's partial; the waves of the first row of tiles add db
-__global__ __launch_bounds__(256) void weight_grad_kernel(const float* __restrict__ A, int64_t lda, const int* __restrict__ rows,
-                                                           int B, int K, const float* __restrict__ G, int ldg, int N,
-                                                           float* __restrict__ ws) {
-    const int lane = threadIdx.x & 63;
-    const int tiles_n = (N + 31) / 32, tiles = (K + 31) / 32 * tiles_n;
-    const int t = 4 * blockIdx.x + (threadIdx.x >> 6);
-    if (t >= tiles) return;
-    const int slice = blockIdx.y, r0 = slice * kSliceRows, r1 = min(B, r0 + kSliceRows);
-    float* part = ws + (size_t)slice * ((size_t)K * N + N);
-    const int tk = t / tiles_n, tn = t % tiles_n;
-    weight_grad_tile(A, lda, rows, r0, r1, K, G, ldg, N, part, tk, tn, lane);
-    if (tk == 0) bias_grad_tile(G, ldg, r0, r1, N, part + (size_t)K * N, tn, lane);
-}
-
-template <bool kWeighted>
-__global__ __launch_bounds__(256) void loss_rows_kernel(const float* __restrict__ Z, float* __restrict__ G, int ld, int B, int C,
-                                                         int loss, const void* __restrict__ targets,
-                                                         const float* __restrict__ row_w, float inv,
-                                                         float* __restrict__ row_loss) {
-    const int row = 4 * blockIdx.x + (threadIdx.x >> 6);
-    if (row >= B) return;
-    loss_row<kWeighted>(Z + (size_t)row * ld, G + (size_t)row * ld, C, loss, targets, row_w, row, inv, row_loss, threadIdx.x & 63);
-}
 
 // One layer of at most 64 outputs; grid = slices, eight waves.  Z / G [B][64].  Every wave reaches both barriers: the loops
 // around them end on their bounds, and row_w changes what a row's pass computes, not which waves run it.
@@ -105,20 +64,6 @@ __global__ __launch_bounds__(512) void fused_step_kernel(const float* __restrict
     }
 }
 
-__global__ __launch_bounds__(256) void loss_sum_kernel(const float* __restrict__ row_loss, int B, double scale, float* __restrict__ out,
-                                                        double* __restrict__ acc) {
-    __shared__ double part[256];
-    loss_sum_block(row_loss, B, scale, out, acc, part);
-}
-
-// element i of a layer's [W | b]: the slices' partials in ascending order, then the decay (kernel elements only), then the optimizer
-__global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ ws, int slices, int n, float* __restrict__ grad,
-                                                     float* __restrict__ P, float* __restrict__ m, float* __restrict__ v, Update u) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    apply_element(sum_partials(ws + i, slices, (size_t)n), (size_t)i, i < u.decay_n, grad, P, m, v, u);
-}
-
 }  // namespace
 }  // namespace bd
 
@@ -141,35 +86,9 @@ int check_call(const bd_trainer_s* t, const float* X, int64_t ldx, const void* t
     return rc < 0 ? rc : check_row_weights(who, row_w, B, B);
 }
 
-void enqueue_forward(bd_trainer_s* t, const float* X, int64_t ldx, const int* rows, int B, hipStream_t stream) {
-    const float* a = X;
-    int64_t lda = ldx;
-    for (int l = 0; l < t->s.n_layers; ++l) {
-        const StackLayer& L = t->s.layers[l];
-        const int act = l + 1 < t->s.n_layers ? L.act : BD_HEAD_LINEAR;
-        hipLaunchKernelGGL(forward_kernel, dim3((B + 63) / 64, (L.n + 63) / 64), dim3(256), 0, stream, a, lda, l == 0 ? rows : nullptr,
-                           B, L.k, t->pool + L.p, L.n, act, t->pool + L.y, L.ld);
-        a = t->pool + L.y;
-        lda = L.ld;
-    }
-}
-
-void enqueue_loss(bd_trainer_s* t, const void* targets, const float* row_w, int B, float* loss_dev, bool accumulate, bool rows_done,
-                  hipStream_t stream) {
-    const StackLayer& L = t->s.last();
-    float *y = t->pool + L.y, *g = t->pool + L.g;
-    if (!rows_done) {
-        const float inv = loss_inv(t->loss, B, L.n);
-        if (row_w)
-            hipLaunchKernelGGL(loss_rows_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, stream, y, g, L.ld, B, L.n, t->loss, targets,
-                               row_w, inv, t->row_loss);
-        else
-            hipLaunchKernelGGL(loss_rows_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, stream, y, g, L.ld, B, L.n, t->loss, targets,
-                               row_w, inv, t->row_loss);
-    }
-    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, stream, t->row_loss, B, loss_scale(t->loss, B, L.n), loss_dev,
-                       accumulate ? t->acc : nullptr);
-}
+// the trainer's pool as a run of one member: no stride is ever multiplied by a member other than 0 (row weights likewise: one
+// row of them, so the calls below give B for ldw)
+StackRun run_of(const bd_trainer_s* t) { return {t->pool, 0, &t->s, t->ws, 0, t->row_loss, 0, t->acc, t->loss}; }
 
 }  // namespace
 }  // namespace bd
@@ -231,42 +150,24 @@ static int do_step(bd_trainer t, const float* X, int64_t ldx, const int32_t* row
     if (rc < 0) return rc;
     hipStream_t stream;
     if ((rc = bd::enter(t, stream_, &stream)) < 0) return rc;
-    const int slices = bd::slices_of(B);
     t->members.advance();
-    bd::Update u = t->members.update_of(t->opt, 0);
-    float* pool = t->pool;
-    const bool fused = t->fused && bd::fusable(t);
-    if (fused) {
+    const bd::Members<1> a = t->members.launch_args<1>(t->opt, 0);
+    const bd::StackRun r = bd::run_of(t);
+    if (t->fused && bd::fusable(t)) {
         const bd::StackLayer& L = t->s.layers[0];
+        const int slices = bd::slices_of(B);
         const float inv = bd::loss_inv(t->loss, B, L.n);
+        float* pool = t->pool;
         if (row_w)
             hipLaunchKernelGGL(bd::fused_step_kernel<true>, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, pool + L.p, L.n,
                                pool + L.y, pool + L.g, L.ld, t->loss, targets, row_w, inv, t->row_loss, t->ws);
         else
             hipLaunchKernelGGL(bd::fused_step_kernel<false>, dim3(slices), dim3(512), 0, stream, X, ldx, rows, B, L.k, pool + L.p, L.n,
                                pool + L.y, pool + L.g, L.ld, t->loss, targets, row_w, inv, t->row_loss, t->ws);
+        bd::stack_loss_sum(r, B, a, nullptr, true, stream);         // the rows' losses and the partials are the kernel's
+        bd::stack_apply(r, t->opt, 0, slices, a, stream);
     } else {
-        bd::enqueue_forward(t, X, ldx, rows, B, stream);
-    }
-    bd::enqueue_loss(t, targets, row_w, B, nullptr, true, fused, stream);
-    for (int l = t->s.n_layers - 1; l >= 0; --l) {
-        const bd::StackLayer& L = t->s.layers[l];
-        const int n = L.k * L.n + L.n;
-        if (!fused) {
-            const float* a = l == 0 ? X : pool + t->s.layers[l - 1].y;
-            const int64_t lda = l == 0 ? ldx : t->s.layers[l - 1].ld;
-            const int tiles = (L.k + 31) / 32 * ((L.n + 31) / 32);
-            hipLaunchKernelGGL(bd::weight_grad_kernel, dim3((tiles + 3) / 4, slices), dim3(256), 0, stream, a, lda,
-                               l == 0 ? rows : nullptr, B, L.k, pool + L.g, L.ld, L.n, t->ws);
-        }
-        if (l > 0) {                                     // with this layer's weights as the forward pass saw them
-            const bd::StackLayer& Lp = t->s.layers[l - 1];
-            hipLaunchKernelGGL(bd::input_grad_kernel, dim3((B + 63) / 64, (L.k + 63) / 64), dim3(256), 0, stream, pool + L.g, L.ld, B,
-                               L.k, pool + L.p, L.n, pool + Lp.y, Lp.act, pool + Lp.g, Lp.ld);
-        }
-        u.decay_n = L.k * L.n;
-        hipLaunchKernelGGL(bd::apply_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, t->ws, slices, n, pool + L.grad, pool + L.p,
-                           bd::slot(pool, L.m), bd::slot(pool, L.v), u);
+        bd::stack_step(r, t->opt, X, ldx, rows, targets, row_w, B, B, a, stream);
     }
     BD_HIP(hipGetLastError());
     return BD_OK;
@@ -288,8 +189,7 @@ static int do_loss(bd_trainer t, const float* X, int64_t ldx, const int32_t* row
     if (!loss_dev) return fail(BD_EINVAL, std::string(who) + ": null loss_dev");
     hipStream_t stream;
     if ((rc = bd::enter(t, stream_, &stream)) < 0) return rc;
-    bd::enqueue_forward(t, X, ldx, rows, B, stream);
-    bd::enqueue_loss(t, targets, row_w, B, loss_dev, false, false, stream);
+    bd::stack_batch_loss(bd::run_of(t), X, ldx, rows, targets, row_w, B, B, bd::members_from<1>(1, 0), loss_dev, stream);
     BD_HIP(hipGetLastError());
     return BD_OK;
 }

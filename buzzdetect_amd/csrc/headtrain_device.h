@@ -2,7 +2,8 @@
 // headbank.hip (a bank of one-layer heads: include/buzzdetect_bank.h) and stackbank.hip (a bank of Dense stacks:
 // include/buzzdetect_stackbank.h).  The three files call these and nothing else for a product, a row's loss, a partial's sum
 // or an update, so a member of a bank and a trainer on its own run the same instructions in the same order: the bit identity
-// the banks promise rests on this file being the only copy.  (headtrain_host.h is its counterpart for the host side.)
+// the banks promise rests on this file being the only copy.  (headtrain_host.h is its counterpart for the host side, and
+// headtrain_stack.h holds the layer-by-layer kernels that headtrain.hip and stackbank.hip both launch.)
 //
 // Every product is one routine, mma_chain: a wave owns a 32 x 32 output tile and walks the reduced index alone in ascending
 // super-steps of 8, in headmlp.hip's operand map (lane l supplies A[i = l & 31][k] and B[k][j = l & 31], lane-half h takes

@@ -1,10 +1,11 @@
 // Host side of the classifier-head trainers, shared by headtrain.hip (one stack: include/buzzdetect_train.h), headbank.hip (a
 // bank of one-layer heads: include/buzzdetect_bank.h) and stackbank.hip (a bank of Dense stacks:
 // include/buzzdetect_stackbank.h), as headtrain_device.h is the one copy of their device routines.  Host code only: no kernel
-// and no device routine lives here.  What the three files keep is what differs between the products - their kernels, the
-// layout of their pools and the launches of their entry points; what they check, how a member's rate, decay, frozen flag,
-// snapshot flag and step count are kept and become launch arguments, where the pieces of a Dense stack lie, and how the
-// running losses and the workspace are read is written here once.
+// and no device routine lives here (the layer-by-layer route of Dense stacks, kernels and launches, is headtrain_stack.h's).
+// What the three files keep is what differs between the products - the kernels that are theirs alone, the layout of their
+// pools and their entry points; what they check, how a member's rate, decay, frozen flag, snapshot flag and step count are
+// kept and become launch arguments, where the pieces of a Dense stack lie, and how the running losses and the workspace are
+// read is written here once.
 //
 // The bias-corrected Adam rate (adam_rate) is part of the bit contract between a trainer and a member of a bank: it is a
 // double expression rounded to float once, and this is its only copy.
@@ -28,17 +29,21 @@ using namespace train;
 
 constexpr int kMembersPerLaunch = 64;
 
-struct Members {                    // the members first .. first + count of a launch, by value
+// The members first .. first + count of a launch, by value.  kCapacity: kMembersPerLaunch for a bank's launches, 1 for a
+// launch of exactly one member (the lone trainer, a stack bank's last member alone), a block of 24 bytes instead of 1 KiB.
+template <int kCapacity>
+struct Members {
     int first, count;
-    float lr[kMembersPerLaunch], lr_t[kMembersPerLaunch], decay[kMembersPerLaunch];
-    int frozen[kMembersPerLaunch];
+    float lr[kCapacity], lr_t[kCapacity], decay[kCapacity];
+    int frozen[kCapacity];
 };
 
 // the launch that starts at member `first` of M: its range, nothing else set
-Members members_from(int M, int first) {
-    Members a{};
+template <int kCapacity = kMembersPerLaunch>
+Members<kCapacity> members_from(int M, int first) {
+    Members<kCapacity> a{};
     a.first = first;
-    a.count = M - first < kMembersPerLaunch ? M - first : kMembersPerLaunch;
+    a.count = M - first < kCapacity ? M - first : kCapacity;
     return a;
 }
 
@@ -75,8 +80,9 @@ struct MemberState {
     }
 
     // the launch arguments of the members from `first` on
-    Members launch_args(const bd_train_optimizer& opt, int first) const {
-        Members a = members_from(size(), first);
+    template <int kCapacity = kMembersPerLaunch>
+    Members<kCapacity> launch_args(const bd_train_optimizer& opt, int first) const {
+        Members<kCapacity> a = members_from<kCapacity>(size(), first);
         for (int j = 0; j < a.count; ++j) {
             const Update u = update_of(opt, first + j);
             a.lr[j] = u.lr;

@@ -1,8 +1,7 @@
 // A bank of Dense stacks (include/buzzdetect_stackbank.h): M members of one shape - 1024 -> widths... -> C, the stacks
 // bd_trainer_create takes - that share each step's rows of X, targets and batch order and differ in parameters, row weights,
-// rate, decay and stopping.  Every kernel is headtrain.hip's layer-by-layer kernel with a member coordinate in the grid, and
-// every product, row loss, partial sum and update is a call into headtrain_device.h: a member's element is the same chain of
-// instructions as the lone trainer's, so its bits are the trainer's.
+// rate, decay and stopping.  Its kernels and their launches are headtrain_stack.h's, the one layer-by-layer training route:
+// bd_trainer_* runs it with one member, this file with M, so a member's bits are the lone trainer's.
 //
 // Layout: member m's block lies at m x `stride` floats of one pool (stride a multiple of 64: the 16-byte row loads of
 // forward_tile / input_grad_tile stay aligned); inside it, at offsets every member shares,
@@ -10,113 +9,19 @@
 //   per layer   y, g                    [max_batch][round_up(n, 32)]: activations (the last: logits) and deltas
 //   row_loss                            [max_batch]
 // The slices' dW / db partials go to a workspace [member][slice][k n + n] of the layer at work, members `ws_stride` apart.
-// A kernel gets member 0's pointers and adds member x stride in 64 bits.
 //
-// Grids: the member is blockIdx.x of the forward, weight-gradient and input-gradient kernels - the coordinate that varies
-// fastest - so the workgroups that read the same rows of X (layer 0: every member reads the same gathered rows) are
-// scheduled next to each other: the rows come from HBM once per step and from cache after that.
+// The members run kMembersPerLaunch at a time; a launch of exactly one member (a bank of one, the 65th of 65) takes the
+// route's one-member argument block, as the lone trainer does.
 //
-// A member's rate, bias-corrected rate, decay and frozen flag travel by value in the launch (Members), kMembersPerLaunch at
-// a time: nothing a later bd_stackbank_set_* could overwrite before the step has run.  The workgroups of a frozen member
-// return at once in the three backward kernels - the first statement, the same for every thread of the workgroup.
-//
-// This file: the stack bank's kernels, the members' blocks in its pool and the launches of its entry points.  The checks, the
-// offsets of a stack's pieces inside a block (StackLayout: the lone trainer's too), Members and the members' state on the host
-// (MemberState), the running losses and the workspace's test hooks are headtrain_host.h's, shared with headtrain.hip and
-// headbank.hip.
+// This file: the stack bank's handle, the members' blocks in its pool (run_of: what the shared route needs to know of them)
+// and its entry points.  The checks, the offsets of a stack's pieces inside a block (StackLayout: the lone trainer's too),
+// Members and the members' state on the host (MemberState), the running losses and the workspace's test hooks are
+// headtrain_host.h's, shared with headtrain.hip and headbank.hip.
 #include "headtrain_device.h"
 #include "headtrain_host.h"
+#include "headtrain_stack.h"
 
 #include "../../include/buzzdetect_stackbank.h"
-
-namespace bd {
-namespace {
-
-// ---- kernels: member = first + the grid's member coordinate; A, P, Y, ... are member 0's ----
-
-// grid (members, ceil(N / 64), ceil(B / 64)): four waves, a 32 x 32 tile each.  a_stride = 0: every member reads the same A (X).
-__global__ __launch_bounds__(256) void stack_forward_kernel(const float* __restrict__ A, int64_t lda, int64_t a_stride,
-                                                             const int* __restrict__ rows, int B, int K,
-                                                             const float* __restrict__ P, int64_t p_stride, int N, int act,
-                                                             float* __restrict__ Y, int64_t y_stride, int ldy, int first) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t member = first + (int)blockIdx.x;
-    const int tr = 2 * blockIdx.z + (wave & 1), tc = 2 * blockIdx.y + (wave >> 1);
-    if (32 * tr >= B || 32 * tc >= N) return;           // (no barrier in this kernel)
-    forward_tile(A + member * a_stride, lda, rows, B, K, P + member * p_stride, N, act, Y + member * y_stride, ldy, tr, tc, lane);
-}
-
-// grid (ceil(B / 4), members): a wave per (row, member)
-template <bool kWeighted>
-__global__ __launch_bounds__(256) void stack_loss_rows_kernel(const float* __restrict__ Z, float* __restrict__ G, int64_t stride,
-                                                               int ld, int B, int C, int loss, const void* __restrict__ targets,
-                                                               const float* __restrict__ row_w, int64_t ldw, float inv,
-                                                               float* __restrict__ row_loss, int first) {
-    const int row = 4 * blockIdx.x + (threadIdx.x >> 6);
-    const int64_t member = first + (int)blockIdx.y;
-    if (row >= B) return;
-    const int64_t at = member * stride + (int64_t)row * ld;
-    loss_row<kWeighted>(Z + at, G + at, C, loss, targets, kWeighted ? row_w + member * ldw : nullptr, row, inv,
-                        row_loss + member * stride, threadIdx.x & 63);
-}
-
-// grid (1, members): member's batch loss to out[member]; its running sum moves unless the member is frozen
-__global__ __launch_bounds__(256) void stack_loss_sum_kernel(const float* __restrict__ row_loss, int64_t stride, int B, double scale,
-                                                              float* __restrict__ out, double* __restrict__ acc, Members a) {
-    __shared__ double part[256];
-    const int64_t member = a.first + (int)blockIdx.y;
-    loss_sum_block(row_loss + member * stride, B, scale, out ? out + member : nullptr,
-                   acc && !a.frozen[blockIdx.y] ? acc + 2 * member : nullptr, part);
-}
-
-// grid (members, ceil(tiles / 4), slices): a wave per 32 x 32 tile of a slice's partial; the waves of the first row of tiles add db
-__global__ __launch_bounds__(256) void stack_weight_grad_kernel(const float* __restrict__ A, int64_t lda, int64_t a_stride,
-                                                                 const int* __restrict__ rows, int B, int K,
-                                                                 const float* __restrict__ G, int64_t g_stride, int ldg, int N,
-                                                                 float* __restrict__ ws, int64_t ws_stride, Members a) {
-    if (a.frozen[blockIdx.x]) return;                    // the whole workgroup; no barrier in this kernel
-    const int lane = threadIdx.x & 63;
-    const int64_t member = a.first + (int)blockIdx.x;
-    const int tiles_n = (N + 31) / 32, tiles = (K + 31) / 32 * tiles_n;
-    const int t = 4 * blockIdx.y + (threadIdx.x >> 6);
-    if (t >= tiles) return;
-    const int slice = blockIdx.z, r0 = slice * kSliceRows, r1 = min(B, r0 + kSliceRows);
-    float* part = ws + member * ws_stride + (size_t)slice * ((size_t)K * N + N);
-    const int tk = t / tiles_n, tn = t % tiles_n;
-    G += member * g_stride;
-    weight_grad_tile(A + member * a_stride, lda, rows, r0, r1, K, G, ldg, N, part, tk, tn, lane);
-    if (tk == 0) bias_grad_tile(G, ldg, r0, r1, N, part + (size_t)K * N, tn, lane);
-}
-
-// grid (members, ceil(K / 64), ceil(B / 64)); G, W, Yp and Gp lie in the members' blocks, `stride` apart
-__global__ __launch_bounds__(256) void stack_input_grad_kernel(const float* __restrict__ G, int ldg, int B, int K,
-                                                                const float* __restrict__ W, int N, const float* __restrict__ Yp,
-                                                                int act_p, float* __restrict__ Gp, int ldp, int64_t stride, Members a) {
-    if (a.frozen[blockIdx.x]) return;                    // the whole workgroup; no barrier in this kernel
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t off = (a.first + (int)blockIdx.x) * stride;
-    const int tr = 2 * blockIdx.z + (wave & 1), tc = 2 * blockIdx.y + (wave >> 1);
-    if (32 * tr >= B || 32 * tc >= K) return;
-    input_grad_tile(G + off, ldg, B, K, W + off, N, Yp + off, act_p, Gp + off, ldp, tr, tc, lane);
-}
-
-// grid (ceil(n / 256), members): element i of the layer's [W | b] of member a.first + blockIdx.y
-__global__ __launch_bounds__(256) void stack_apply_kernel(const float* __restrict__ ws, int64_t ws_stride, int slices, int n, int decay_n,
-                                                           float* __restrict__ grad, float* __restrict__ P, float* __restrict__ m,
-                                                           float* __restrict__ v, int64_t stride, int kind, float b1, float b2, float eps,
-                                                           Members a) {
-    const int j = blockIdx.y;
-    if (a.frozen[j]) return;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t off = (a.first + j) * stride;
-    const Update u{kind, a.lr[j], b1, b2, eps, a.lr_t[j], a.decay[j], decay_n};
-    apply_element(sum_partials(ws + (a.first + j) * ws_stride + i, slices, (size_t)n), (size_t)i, i < decay_n, grad + off, P + off,
-                  m ? m + off : nullptr, v ? v + off : nullptr, u);
-}
-
-}  // namespace
-}  // namespace bd
 
 struct bd_stackbank_s : bd::TrainHandle {
     int M = 0;
@@ -129,38 +34,8 @@ struct bd_stackbank_s : bd::TrainHandle {
 namespace bd {
 namespace {
 
-// the forward pass of members a.first ..: the last layer's output goes to Y (member 0's, members y_stride apart, rows ldy
-// apart) where given, else to the layer's own logits
-void enqueue_forward(bd_stackbank_s* b, const float* X, int64_t ldx, const int* rows, int B, const Members& a, float* Y, int64_t y_stride,
-                     int ldy, hipStream_t stream) {
-    const float* src = X;
-    int64_t lda = ldx, a_stride = 0;
-    for (int l = 0; l < b->s.n_layers; ++l) {
-        const StackLayer& L = b->s.layers[l];
-        const bool last = l + 1 == b->s.n_layers;
-        const bool outside = last && Y;
-        hipLaunchKernelGGL(stack_forward_kernel, dim3(a.count, (L.n + 63) / 64, (B + 63) / 64), dim3(256), 0, stream, src, lda, a_stride,
-                           l == 0 ? rows : nullptr, B, L.k, b->pool + L.p, b->stride, L.n, last ? BD_HEAD_LINEAR : L.act,
-                           outside ? Y : b->pool + L.y, outside ? y_stride : b->stride, outside ? ldy : L.ld, a.first);
-        src = b->pool + L.y;
-        lda = L.ld;
-        a_stride = b->stride;
-    }
-}
-
-void enqueue_loss(bd_stackbank_s* b, const void* targets, const float* row_w, int64_t ldw, int B, float* loss_dev, bool accumulate,
-                  const Members& a, hipStream_t stream) {
-    const StackLayer& L = b->s.last();
-    const float inv = loss_inv(b->loss, B, L.n);
-    float* row_loss = b->pool + b->off_row_loss;
-    if (row_w)
-        hipLaunchKernelGGL(stack_loss_rows_kernel<true>, dim3((B + 3) / 4, a.count), dim3(256), 0, stream, b->pool + L.y, b->pool + L.g,
-                           b->stride, L.ld, B, L.n, b->loss, targets, row_w, ldw, inv, row_loss, a.first);
-    else
-        hipLaunchKernelGGL(stack_loss_rows_kernel<false>, dim3((B + 3) / 4, a.count), dim3(256), 0, stream, b->pool + L.y, b->pool + L.g,
-                           b->stride, L.ld, B, L.n, b->loss, targets, row_w, ldw, inv, row_loss, a.first);
-    hipLaunchKernelGGL(stack_loss_sum_kernel, dim3(1, a.count), dim3(256), 0, stream, row_loss, b->stride, B, loss_scale(b->loss, B, L.n),
-                       loss_dev, accumulate ? b->acc : nullptr, a);
+StackRun run_of(const bd_stackbank_s* b) {
+    return {b->pool, b->stride, &b->s, b->ws, b->ws_stride, b->pool + b->off_row_loss, b->stride, b->acc, b->loss};
 }
 
 // every layer of the member's parameters -> its snapshot (to_snapshot) or back, on the caller's stream
@@ -239,31 +114,12 @@ int bd_stackbank_step(bd_stackbank b, const float* X, int64_t ldx, const int32_t
     if (rc < 0) return rc;
     hipStream_t stream;
     if ((rc = bd::enter(b, stream_, &stream)) < 0) return rc;
-    const int slices = bd::slices_of(B);
     b->members.advance();
-    float* pool = b->pool;
-    for (int first = 0; first < b->M; first += bd::kMembersPerLaunch) {
-        const bd::Members a = b->members.launch_args(b->opt, first);
-        bd::enqueue_forward(b, X, ldx, rows, B, a, nullptr, 0, 0, stream);
-        bd::enqueue_loss(b, targets, row_w, ldw, B, nullptr, true, a, stream);
-        for (int l = b->s.n_layers - 1; l >= 0; --l) {
-            const bd::StackLayer& L = b->s.layers[l];
-            const int n = L.k * L.n + L.n;
-            const int tiles = (L.k + 31) / 32 * ((L.n + 31) / 32);
-            hipLaunchKernelGGL(bd::stack_weight_grad_kernel, dim3(a.count, (tiles + 3) / 4, slices), dim3(256), 0, stream,
-                               l == 0 ? X : pool + b->s.layers[l - 1].y, l == 0 ? ldx : (int64_t)b->s.layers[l - 1].ld,
-                               l == 0 ? (int64_t)0 : b->stride, l == 0 ? rows : nullptr, B, L.k, pool + L.g, b->stride, L.ld, L.n, b->ws,
-                               b->ws_stride, a);
-            if (l > 0) {                                 // with this layer's weights as the forward pass saw them
-                const bd::StackLayer& Lp = b->s.layers[l - 1];
-                hipLaunchKernelGGL(bd::stack_input_grad_kernel, dim3(a.count, (L.k + 63) / 64, (B + 63) / 64), dim3(256), 0, stream,
-                                   pool + L.g, L.ld, B, L.k, pool + L.p, L.n, pool + Lp.y, Lp.act, pool + Lp.g, Lp.ld, b->stride, a);
-            }
-            hipLaunchKernelGGL(bd::stack_apply_kernel, dim3((n + 255) / 256, a.count), dim3(256), 0, stream, b->ws, b->ws_stride, slices, n,
-                               L.k * L.n, pool + L.grad, pool + L.p, bd::slot(pool, L.m), bd::slot(pool, L.v), b->stride, b->opt.kind,
-                               b->opt.beta_1, b->opt.beta_2, b->opt.epsilon, a);
-        }
-    }
+    const bd::StackRun r = bd::run_of(b);
+    bd::for_each_launch(b->M, [&](int first, auto capacity) {
+        constexpr int kCapacity = decltype(capacity)::value;
+        bd::stack_step(r, b->opt, X, ldx, rows, targets, row_w, ldw, B, b->members.launch_args<kCapacity>(b->opt, first), stream);
+    });
     BD_HIP(hipGetLastError());
     return BD_OK;
 }
@@ -277,11 +133,11 @@ int bd_stackbank_loss(bd_stackbank b, const float* X, int64_t ldx, const int32_t
     if (rc < 0) return rc;
     hipStream_t stream;
     if ((rc = bd::enter(b, stream_, &stream)) < 0) return rc;
-    for (int first = 0; first < b->M; first += bd::kMembersPerLaunch) {
-        const bd::Members a = bd::members_from(b->M, first);
-        bd::enqueue_forward(b, X, ldx, rows, B, a, nullptr, 0, 0, stream);
-        bd::enqueue_loss(b, targets, row_w, ldw, B, loss_dev, false, a, stream);
-    }
+    const bd::StackRun r = bd::run_of(b);
+    bd::for_each_launch(b->M, [&](int first, auto capacity) {
+        constexpr int kCapacity = decltype(capacity)::value;
+        bd::stack_batch_loss(r, X, ldx, rows, targets, row_w, ldw, B, bd::members_from<kCapacity>(b->M, first), loss_dev, stream);
+    });
     BD_HIP(hipGetLastError());
     return BD_OK;
 }
@@ -297,8 +153,11 @@ int bd_stackbank_forward(bd_stackbank b, const float* X, int64_t ldx, const int3
         return fail(BD_EINVAL, std::string(who) + ": logits_dev must be float-aligned with ldl >= M C");
     hipStream_t stream;
     if ((rc = bd::enter(b, stream_, &stream)) < 0) return rc;
-    for (int first = 0; first < b->M; first += bd::kMembersPerLaunch)
-        bd::enqueue_forward(b, X, ldx, rows, B, bd::members_from(b->M, first), logits_dev, C, (int)ldl, stream);
+    const bd::StackRun r = bd::run_of(b);
+    bd::for_each_launch(b->M, [&](int first, auto capacity) {
+        constexpr int kCapacity = decltype(capacity)::value;
+        bd::stack_forward(r, X, ldx, rows, B, bd::members_from<kCapacity>(b->M, first), logits_dev, C, (int)ldl, stream);
+    });
     BD_HIP(hipGetLastError());
     return BD_OK;
 }

@@ -14,8 +14,9 @@
  * The contract is the bank's, for stacks: after any sequence of calls, member m's parameters, Adam slots, last gradients of
  * every layer, logits, batch loss and running mean loss equal, bit for bit, those of a bd_trainer created from member m's
  * initial layers that received the same calls - bd_trainer_step_weighted with row m of the weights, or bd_trainer_step where
- * the bank got NULL.  It holds by construction: csrc/stackbank.hip's kernels are the lone trainer's layer-by-layer kernels
- * with a member coordinate in the grid, and call csrc/headtrain_device.h for every product, row loss, partial sum and update.
+ * the bank got NULL.  It holds by construction: the bank's kernels and launches (csrc/headtrain_stack.h) are the ones the
+ * lone trainer's layer-by-layer route runs with one member, and call csrc/headtrain_device.h for every product, row loss,
+ * partial sum and update.
  * Slices are the same BD_TRAIN_SLICE_ROWS rows and a member's partials are added in ascending slice order; nothing is added
  * atomically; nothing depends on the grid, the number of compute units, M, or a member's place in the bank.
  *

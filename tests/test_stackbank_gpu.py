@@ -223,6 +223,21 @@ def test_a_members_bits_do_not_depend_on_its_place_or_its_company(data):
 
 
 # ---------------------------------------------------------------------------------------------------- 3. frozen, snapshot
+@pytest.mark.parametrize("m,place", ((1, 0), (65, 64)))
+def test_a_frozen_member_alone_in_its_launch_skips_the_steps_too(data, m, place):
+    """A launch of exactly one member (a bank of one; member 64 of 65) leaves a frozen member's backward launches out on the
+    host instead of returning from them: the member still continues as the trainer that skipped those steps."""
+    _, x_dev = data
+    shape, batch, loss = (33, 2), 257, "categorical"
+    acts = activations_of(shape, 2)
+    members = [make_member(shape, acts, 400 + j) for j in range(m)]
+    steps = make_steps(np.random.default_rng(11), 2, m, batch, True, loss, True, n_steps=4)
+    bank = run_bank(x_dev, members, loss, "adam", batch, steps, frozen_at={1: [(place, True)], 3: [(place, False)]})
+    assert_member_is_trainer(bank, place, run_trainer(x_dev, members[place], place, loss, "adam", batch, steps, (1, 2)), f"M={m}")
+    if m > 1:                                                # its neighbour in the other launch took every step
+        assert_member_is_trainer(bank, 0, run_trainer(x_dev, members[0], 0, loss, "adam", batch, steps), f"M={m}, member 0")
+
+
 @pytest.mark.parametrize("optimizer", ("sgd", "adam"))
 def test_a_frozen_member_keeps_every_layer_and_continues_as_a_trainer_that_skipped_the_steps(data, optimizer):
     _, x_dev = data

@@ -41,6 +41,9 @@ def test_the_stack_bank_calls_the_shared_device_routines_and_defines_none():
     shared = open(os.path.join(build.CSRC, "headtrain_device.h")).read()
     text = open(os.path.join(build.CSRC, "stackbank.hip")).read()
     assert '#include "headtrain_device.h"' in text
+    # its kernels are the layer-by-layer route's, which it includes: what holds for the file holds for the two together
+    assert '#include "headtrain_stack.h"' in text and "headtrain_stack.h" in build.HEADERS
+    text += open(os.path.join(build.CSRC, "headtrain_stack.h")).read()
     assert '#include "headtrain_host.h"' in text and "headtrain_host.h" in build.HEADERS       # the shared host side
     for name in ("mma_chain", "forward_tile", "input_grad_tile", "weight_grad_tile", "bias_grad_tile", "loss_row", "acc_row",
                  "loss_sum_block", "sum_partials", "decayed", "apply_element"):

@@ -1,7 +1,8 @@
 """The host side the three training families share (buzzdetect_amd/csrc/headtrain_host.h: the lone trainer, the bank of heads,
 the bank of stacks): the header is built and hashed, the three .hip files include it and define none of its routines again, the
-bias-corrected Adam rate is written once, and every refusal gives the return code and the words recorded before the host side
-was shared (tests/golden/train_refusals.json, tools/record_train_refusals.py).  No GPU needed."""
+layer-by-layer route of Dense stacks (headtrain_stack.h) is the one copy of its kernels and launches for the lone trainer and
+the bank of stacks, the bias-corrected Adam rate is written once, and every refusal gives the return code and the words
+recorded before the host side was shared (tests/golden/train_refusals.json, tools/record_train_refusals.py).  No GPU needed."""
 import ctypes as C
 import json
 import os
@@ -21,11 +22,21 @@ SHARED_FUNCTIONS = ("check_training_setup", "check_stack", "select_device", "che
                     "enter_and_wait")
 FORMER_COPIES = ("check_weights", "members_of", "inv_of", "scale_of", "width_of")      # the names the copies had
 SHARED_TYPES = ("Members", "MemberState", "TrainHandle", "StackLayer", "StackLayout")
+STACK_HEADER = "headtrain_stack.h"                              # the layer-by-layer route headtrain.hip and stackbank.hip run
+STACK_SOURCES = ("headtrain.hip", "stackbank.hip")
+STACK_KERNELS = ("stack_forward_kernel", "stack_loss_rows_kernel", "stack_loss_sum_kernel", "stack_weight_grad_kernel",
+                 "stack_input_grad_kernel", "stack_apply_kernel")
 
 
 def read(name):
     with open(os.path.join(build.CSRC, name)) as f:
         return f.read()
+
+
+def read_with_stack_header(name):
+    """The file, and behind it the stack header if the file includes it: where a call may have moved to."""
+    text = read(name)
+    return text + read(STACK_HEADER) if '#include "' + STACK_HEADER + '"' in text else text
 
 
 def defines_function(name, text):
@@ -41,6 +52,23 @@ def test_the_host_header_is_built_hashed_and_included():
         text = read(source)
         assert '#include "headtrain_host.h"' in text, source
         assert text.index('#include "headtrain_device.h"') < text.index('#include "headtrain_host.h"'), source
+    assert STACK_HEADER in build.HEADERS and os.path.exists(os.path.join(build.CSRC, STACK_HEADER))
+    for source in SOURCES:
+        text = read(source)
+        assert ('#include "' + STACK_HEADER + '"' in text) == (source in STACK_SOURCES), source
+        if source in STACK_SOURCES:
+            assert text.index('#include "headtrain_host.h"') < text.index('#include "' + STACK_HEADER + '"'), source
+
+
+def test_the_layer_by_layer_kernels_are_written_once():
+    kernels = {source: re.findall(r"__global__\s+(?:__launch_bounds__\(\d+\)\s+)?void\s+(\w+)\s*\(", read(source))
+               for source in STACK_SOURCES + (STACK_HEADER,)}
+    assert kernels["headtrain.hip"] == ["fused_step_kernel"] and read("headtrain.hip").count("__global__") == 1
+    assert kernels["stackbank.hip"] == [] and "__global__" not in read("stackbank.hip")
+    assert sorted(kernels[STACK_HEADER]) == sorted(STACK_KERNELS)
+    for source in STACK_SOURCES:
+        assert "hipLaunchKernelGGL(" not in read(source).replace("hipLaunchKernelGGL(bd::fused_step_kernel<", ""), source
+        assert re.search(r"\bStackRun run_of\(", read(source)), source
 
 
 def test_the_host_header_holds_host_code_only():
@@ -73,17 +101,17 @@ def test_no_training_file_defines_a_shared_routine_again():
     assert "fill_kernel" not in read("headtrain.hip")       # the workspace is filled the banks' way
     # the calls the three families have in common go through the one copy
     for source in SOURCES:
-        text = read(source)
+        text = read_with_stack_header(source)
         for name in ("check_training_setup", "select_device", "check_batch", "check_row_weights", "enter", "set_learning_rate",
                      "set_weight_decay", "mean_losses", "workspace_floats", "workspace_fill", "workspace_read", "destroy", "loss_inv",
                      "loss_scale", "slices_of"):
             assert re.search(r"\b" + name + r"\(", text), f"{source} does not call {name}"
     for source in ("headbank.hip", "stackbank.hip"):
-        text = read(source)
+        text = read_with_stack_header(source)
         for name in ("launch_args", "members_from", "set_frozen", "snapshot_member", "restore_member", "check_member"):
-            assert re.search(r"\b" + name + r"\(", text), f"{source} does not call {name}"
-    for source in ("headtrain.hip", "stackbank.hip"):
-        text = read(source)
+            assert re.search(r"\b" + name + r"(<\w+>)?\(", text), f"{source} does not call {name}"      # (<capacity>: of a launch)
+    for source in STACK_SOURCES:
+        text = read_with_stack_header(source)
         for name in ("check_stack", "stack_layout", "upload_stack", "copy_stack", "read_stack_pair"):
             assert re.search(r"\b" + name + r"\(", text), f"{source} does not call {name}"
 
@@ -97,8 +125,9 @@ def test_the_adam_rate_is_written_once():
     assert header.count("std::pow(") == 2                    # beta_2^t and beta_1^t of the one expression
     # the trainer's update and a bank's launch arguments are built from it by one routine
     assert header.count("adam_rate(") == 2 and len(re.findall(r"\bupdate_of\(", header)) == 2
-    assert re.search(r"\bupdate_of\(", read("headtrain.hip"))
-    for source in SOURCES:
+    # (the trainer's update is the launch arguments of its one member: launch_args, which calls update_of)
+    assert re.search(r"\blaunch_args<1>\(", read("headtrain.hip")) and re.search(r"= update_of\(", header)
+    for source in SOURCES + (STACK_HEADER,):
         assert "adam_rate(" not in read(source) and "std::sqrt(" not in read(source), source
 
 
