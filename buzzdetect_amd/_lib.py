@@ -440,6 +440,25 @@ EVAL_PROTOTYPES = {
                                           C.c_void_p, C.c_void_p]),
 }
 
+ROWS_ABI_VERSION = 1
+ROWS_CODECS = {"f32": 0, "h": 1, "b": 2}
+ROWS_SLICE = 256
+ROWS_HEADER_BYTES = 16
+ROWS_MAX_WINDOWS = 1 << 24
+ROWS_BAD_EXPONENT = -(1 << 31)      # the record of a row that is not representable; it decodes to quiet NaN
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_rows.h
+ROWS_PROTOTYPES = {
+    "bd_rows_abi_version": (C.c_int, []),
+    "bd_rows_record_bytes": (C.c_int64, [C.c_int32]),
+    "bd_rows_encode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_rows_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_rows_encode_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_rows_decode_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_score_rows_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "bd_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -475,7 +494,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ENSEMBLE_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
             + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()) \
-            + list(EVAL_PROTOTYPES.items()):
+            + list(EVAL_PROTOTYPES.items()) + list(ROWS_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -509,6 +528,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: calls ABI version {lib.bd_calls_abi_version()} != {CALLS_ABI_VERSION}; rebuild")
     if lib.bd_eval_abi_version() != EVAL_ABI_VERSION:
         raise RuntimeError(f"{path}: eval ABI version {lib.bd_eval_abi_version()} != {EVAL_ABI_VERSION}; rebuild")
+    if lib.bd_rows_abi_version() != ROWS_ABI_VERSION:
+        raise RuntimeError(f"{path}: rows ABI version {lib.bd_rows_abi_version()} != {ROWS_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

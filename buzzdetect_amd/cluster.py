@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from . import _lib, framing
-from .dataset import DIGITS_TIME, FRAMELENGTH_S, _embed_parts, _open_engine, _torch
+from .dataset import DIGITS_TIME, FRAMELENGTH_S, _embed_parts, _open_engine, _part_windows, _torch
 from .search import ANNOTATION_COLUMNS, _end, _walk, norms_host, pack_queries
 
 CLUSTER_COLUMNS = ("ident", "start", "end", "cluster", "distance")
@@ -492,7 +492,7 @@ class _RowStore:
 
 
 def _set_windows(engine, parts, hop: int, step: int) -> int:
-    return sum(int(engine.num_windows(int(p.numel()), hop, step)) for p in parts)
+    return sum(_part_windows(engine, p, hop, step) for p in parts)
 
 
 def cluster_recordings(dir_audio: str, n_clusters: int, *, metric: str = "cosine", engine=None, framehop_prop: float = 1.0,

@@ -8,6 +8,7 @@
 #include "engine_state.h"
 
 #include "../../include/buzzdetect_head.h"
+#include "../../include/buzzdetect_rows.h"
 
 namespace {
 
@@ -620,6 +621,51 @@ int bd_stage_tap(bd_handle h, const float* pcm_dev, int64_t n_samples, int32_t h
     if (stage < 0 || stage >= BD_NUM_STAGES) return fail(BD_EINVAL, "bd_stage_tap: stage out of range");
     return run_packed(h, pcm_dev, &n_samples, 1, hop_samples, patch_step, workspace_dev, workspace_bytes, nullptr,
                       nullptr, stage, windows, out_dev, (hipStream_t)stream);
+}
+
+// The scratch of the attached heads for one group of bd_score_rows: the regions attached_head carves (a set's three, and the
+// wide rows of an ensemble behind them); the packaged head needs none
+static int64_t score_rows_scratch(const bd_engine* e, int64_t windows) {
+    if (!e->set.dev) return 0;
+    const int64_t group = windows < e->group_windows ? windows : e->group_windows;
+    return group * (bd::kHeadSetRegions + 1) * bd::kHeadSetRow * (int64_t)sizeof(float);
+}
+
+int64_t bd_score_rows_workspace_bytes(bd_handle h, int64_t windows) {
+    if (!h) return fail(BD_EINVAL, "bd_score_rows_workspace_bytes: null handle");
+    if (windows < 0 || windows > BD_ROWS_MAX_WINDOWS)
+        return fail(BD_EINVAL, "bd_score_rows_workspace_bytes: windows = " + std::to_string(windows) + ", a call takes 0.." +
+                                   std::to_string(BD_ROWS_MAX_WINDOWS));
+    if (h->n_classes == 0) return fail(BD_EINVAL, "bd_score_rows_workspace_bytes: engine was created without a head");
+    return score_rows_scratch(h, windows);
+}
+
+int bd_score_rows(bd_handle h, const float* rows_dev, int64_t windows, float* logits_dev, void* workspace_dev,
+                  int64_t workspace_bytes, void* stream) {
+    if (!h) return fail(BD_EINVAL, "bd_score_rows: null handle");
+    if (h->n_classes == 0) return fail(BD_EINVAL, "bd_score_rows: engine was created without a head");
+    if (windows < 0 || windows > BD_ROWS_MAX_WINDOWS)
+        return fail(BD_EINVAL, "bd_score_rows: windows = " + std::to_string(windows) + ", a call takes 0.." +
+                                   std::to_string(BD_ROWS_MAX_WINDOWS));
+    if (windows == 0) return BD_OK;
+    if (!rows_dev || misaligned(rows_dev)) return fail(BD_EINVAL, "bd_score_rows: rows_dev is null or not 16-byte aligned");
+    if (!logits_dev || misaligned(logits_dev)) return fail(BD_EINVAL, "bd_score_rows: logits_dev is null or not 16-byte aligned");
+    const int64_t need = score_rows_scratch(h, windows);
+    if (misaligned(workspace_dev)) return fail(BD_EINVAL, "bd_score_rows: workspace_dev is not 16-byte aligned");
+    if (need > 0 && (!workspace_dev || workspace_bytes < need))
+        return fail(BD_EWORKSPACE, "bd_score_rows: workspace smaller than bd_score_rows_workspace_bytes()");
+    BD_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->profiling) mark(h, s, -1);
+    for (int64_t w0 = 0; w0 < windows; w0 += h->group_windows) {
+        const int gw = (int)(windows - w0 < h->group_windows ? windows - w0 : h->group_windows);
+        Group g{h, nullptr, s, nullptr, nullptr, 0, (int)w0, gw, nullptr, nullptr, nullptr, logits_dev + w0 * h->n_classes};
+        const float* pooled = rows_dev + w0 * BD_EMBEDDING_SIZE;
+        const int rc = h->set.dev ? attached_head(g, pooled, static_cast<float*>(workspace_dev)) : head(g, pooled);
+        if (rc < 0) return rc;
+    }
+    BD_HIP(hipGetLastError());
+    return BD_OK;
 }
 
 int bd_debug_pointwise(const float* a_dev, const float* wt_dev, const float* bias_dev, float* c_dev, int64_t m,

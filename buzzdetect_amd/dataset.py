@@ -258,9 +258,47 @@ def _torch():
     return torch
 
 
+def _store_of(dir_audio):
+    """The embedding store ``dir_audio`` is (a ``store.Store``, or a folder that holds one), else None: audio."""
+    from . import store
+    return store.as_store(dir_audio)
+
+
+def _sources(dir_audio, engine, framehop_prop: float, chunklength: float, annotations: Annotations, only_annotated: bool,
+             messages: List[str]):
+    """(ident, chunks) of every recording the tools walk, in order: from audio (``_recordings``, ``_read_chunks``; ``chunklength``
+    already rounded), or from an embedding store, whose chunks' ``pcm`` are handles on stored rows (``store.StoredPart``) and
+    whose parameters must be the caller's."""
+    st = _store_of(dir_audio)
+    if st is not None:
+        yield from st.walk(engine, framehop_prop, chunklength, annotations, only_annotated, messages)
+        return
+    group = 0
+    for path, ident in _recordings(dir_audio, annotations, only_annotated, messages):
+        chunks = _read_chunks(engine, path, ident, group, chunklength, messages)
+        if chunks:
+            group += 1
+            yield ident, chunks
+
+
+def _stored(parts) -> bool:
+    return bool(parts) and hasattr(parts[0], "stored_rows")
+
+
+def _part_windows(engine, part, hop: int, step: int) -> int:
+    """Windows of one part: a chunk of audio at 16 kHz, or a handle on stored rows."""
+    if hasattr(part, "stored_rows"):
+        return int(part.windows)
+    return int(engine.num_windows(int(part.numel()), hop, step))
+
+
 def _embed_parts(engine, parts, hop: int, step: int):
     """One launch set's embeddings, final: the set's range verdict is waited for, and a flagged set is computed again with
-    exact-f32 products, as ``engine.embed`` does for its one chunk.  Returns (rows, windows per part)."""
+    exact-f32 products, as ``engine.embed`` does for its one chunk.  Returns (rows, windows per part).  Parts of an embedding
+    store are read and decoded instead (``store.stored_rows``): no embedder launch."""
+    if _stored(parts):
+        from .store import stored_rows
+        return stored_rows(engine, parts)
     from .engine import LaunchVerdict
     f16 = engine._mode != "f32"
     verdict = LaunchVerdict(engine._stream()) if f16 else None
@@ -297,7 +335,9 @@ def embed_annotated(dir_audio: str, annotations, classes: Sequence[str], *, engi
     ``annotations`` (a path for ``read_annotations`` or what it returns).  Same chunks, same resampling, same windows as
     ``analyze(framehop_prop=..., chunklength=...)``: ``starts`` is that run's ``start`` column.  A recording without
     annotation rows is all background (``only_annotated=True`` leaves such recordings out).  Ambiguous windows
-    (``label_windows``) are left out.  ``engine``: a ``HipEngine`` to use; else one is built for ``embeddername`` and closed."""
+    (``label_windows``) are left out.  ``engine``: a ``HipEngine`` to use; else one is built for ``embeddername`` and closed.
+    ``dir_audio`` may be an embedding store (``store.embed_recordings``: its folder, or a ``store.Store``) made with the same
+    ``framehop_prop`` and ``chunklength``: the rows are then read, not computed, and the set is the same."""
     from .engine import hop_samples, patch_step
     torch = _torch()
     classes = list(classes)
@@ -309,13 +349,10 @@ def embed_annotated(dir_audio: str, annotations, classes: Sequence[str], *, engi
     engine, own = _open_engine(engine, embeddername)
     try:
         idents, emb_rows, tgt_rows, grp_rows, start_rows = [], [], [], [], []
-        for path, ident in _recordings(dir_audio, notes, only_annotated, messages):
-            chunks = _read_chunks(engine, path, ident, len(idents), chunklength, messages)
-            if not chunks:
-                continue
+        for ident, chunks in _sources(dir_audio, engine, framehop_prop, chunklength, notes, only_annotated, messages):
             idents.append(ident)
             parts = [c.pcm for c in chunks]
-            windows = [engine.num_windows(int(p.numel()), hop, step) for p in parts]
+            windows = [_part_windows(engine, p, hop, step) for p in parts]
             for a, b in _launch_sets(parts, windows):
                 emb, counts = _embed_parts(engine, parts[a:b], hop, step)
                 at = 0
@@ -502,8 +539,11 @@ def augment(dir_audio: str, annotations, classes: Sequence[str], *, snr_db=(0, 5
     and gain, and the 64 mixtures are the 64 parts of one ``engine.launch``: each keeps its own end-of-chunk padding, so its
     rows are those of ``engine.embed(mixture)``.  Targets and ``starts`` are the event clip's windows'; ``groups`` is the
     event's recording.  A mixture whose background came out silent (``bd_mix``'s flag) is dropped, marked in ``plan`` and
-    counted in ``messages``.  The same folder, annotations and seed give the same bits."""
+    counted in ``messages``.  The same folder, annotations and seed give the same bits.  Mixing needs the audio: an embedding
+    store in place of ``dir_audio`` is refused (``ValueError``)."""
     from .engine import hop_samples, patch_step
+    if _store_of(dir_audio) is not None:
+        raise ValueError("augment mixes audio and needs the recordings themselves: an embedding store holds none")
     torch = _torch()
     classes = list(classes)
     notes = _as_annotations(annotations)

@@ -272,6 +272,8 @@ class HipEngine:
         self.device = torch.device("cuda", self.device_index)
 
         blob = np.ascontiguousarray(blob, dtype=np.float32)
+        self.embeddername = embeddername
+        self._blob, self._weights_sha256 = blob, None      # (hashed when an embedding store first asks: weights_sha256)
         mel = np.ascontiguousarray(weights.load_mel(embeddername), dtype=np.float32)
         w = _lib.bd_weights()
         w.embedder_blob = blob.ctypes.data_as(C.POINTER(C.c_float))
@@ -408,6 +410,16 @@ class HipEngine:
         if rows.ndim != 2 or rows.shape[1] != self.n_classes:
             raise ValueError(f"split() takes [windows, {self.n_classes}] rows, not {tuple(rows.shape)}")
         return {name: rows[:, cols] for name, cols in self.member_columns.items()}
+
+    @property
+    def weights_sha256(self) -> str:
+        """SHA-256 of the embedder weights as loaded (the float32 blob ``bd_create`` took): what an embedding store records,
+        and what it asks of an engine that reads it."""
+        if self._weights_sha256 is None:
+            import hashlib
+            self._weights_sha256 = hashlib.sha256(self._blob.tobytes()).hexdigest()
+            self._blob = None
+        return self._weights_sha256
 
     # ------------------------------------------------------------------ lifecycle
     def close(self) -> None:
@@ -799,6 +811,40 @@ class HipEngine:
         verdict = LaunchVerdict(stream) if f16 else None
         _, logits = self.run(x, hop, step, False, True, out=out, verdict=verdict)
         return DeviceResult(logits, stream, self, self._redo_on(stream, x, hop, step, False, out=out) if f16 else None, verdict)
+
+    def score_rows(self, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The engine's heads on embeddings that are already on the device (``bd_score_rows``): ``rows`` float32 [W, 1024] ->
+        the logits [W, n_classes] on the current stream, bit for bit what ``predict`` gives for windows with these embeddings,
+        whatever the head (the packaged one, a stack, a set, an ensemble).  No CNN launch; the heads' scratch is a buffer of its
+        own, not the pass's workspace.  ``out``: optional caller-owned rows to write into."""
+        if self.n_classes == 0:
+            raise RuntimeError("engine was created without a classifier head")
+        if (not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[1] != _lib.EMBEDDING_SIZE or rows.dtype != torch.float32
+                or rows.device != self.device or not rows.is_contiguous() or rows.data_ptr() % 16):
+            raise ValueError(f"rows must be a contiguous, 16-byte aligned float32 [W, {_lib.EMBEDDING_SIZE}] tensor on {self.device}")
+        w = int(rows.shape[0])
+        if out is None:
+            out = self._empty((w, self.n_classes))
+        elif (tuple(out.shape) != (w, self.n_classes) or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous() or out.data_ptr() % 16):
+            raise ValueError(f"out must be a contiguous, 16-byte aligned float32 [{w}, {self.n_classes}] tensor on {self.device}")
+        stream = self._stream()
+        with self._lock, torch.cuda.device(self.device):
+            need = _lib.check(self._lib.bd_score_rows_workspace_bytes(self._handle, w))
+            ws = self._score_ws(need)
+            _lib.check(self._lib.bd_score_rows(self._handle, rows.data_ptr() if w else None, w, out.data_ptr() if w else None,
+                                               ws.data_ptr() if ws is not None else None, need, stream.cuda_stream))
+        rows.record_stream(stream)
+        return out
+
+    def _score_ws(self, nbytes: int) -> Optional[torch.Tensor]:
+        """The scratch of ``score_rows``, exactly ``nbytes`` long (a seam for tests that hand out guarded memory); None for 0."""
+        if nbytes == 0:
+            return None
+        ws = getattr(self, "_score_workspace", None)
+        if ws is None or ws.numel() != nbytes:
+            ws = self._score_workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        return ws
 
     def stage_tap(self, samples, hop: int, step: int, stage: int, windows: int) -> torch.Tensor:
         """Test hook: NHWC activation after CNN stage ``stage`` for the first ``windows`` windows."""

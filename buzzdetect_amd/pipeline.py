@@ -82,6 +82,14 @@ class Member:
     digits_results: int
     threshold: Optional[float]
 
+    def csv(self, rows: "np.ndarray", framehop_s: float, digits_time: int, time_start: float) -> Tuple[bytes, bytes]:
+        """(header line, rows) of one chunk in this model's result file: its columns of the engine's rows, as activations or as
+        detections (the writer's text, and ``store.score_store``'s)."""
+        own = np.ascontiguousarray(rows[:, self.columns])
+        if self.threshold is None:
+            return results.activation_csv(own, self.classes, framehop_s, digits_time, time_start, self.classes_out, self.digits_results)
+        return results.detection_csv(own, self.threshold, self.classes, framehop_s, digits_time, time_start)
+
 
 @dataclass
 class MemberFile:
@@ -873,14 +881,7 @@ class Pipeline:
                     at += n
                     if t.job.outputs is not None:          # a set of heads: the chunk's rows once per member of this job
                         for mf in t.job.outputs:
-                            m = self.members[mf.member]
-                            own = np.ascontiguousarray(rows[:, m.columns])
-                            if m.threshold is None:
-                                head, body = results.activation_csv(own, m.classes, self.framehop_s, self.digits_time, t.chunk[0],
-                                                                    m.classes_out, m.digits_results)
-                            else:
-                                head, body = results.detection_csv(own, m.threshold, m.classes, self.framehop_s,
-                                                                   self.digits_time, t.chunk[0])
+                            head, body = self.members[mf.member].csv(rows, self.framehop_s, self.digits_time, t.chunk[0])
                             t1 = time.perf_counter()
                             mf.rf.append_text(head, body)
                             t_io += time.perf_counter() - t1

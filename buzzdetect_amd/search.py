@@ -30,8 +30,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, framing
-from .dataset import (DIGITS_TIME, FRAMELENGTH_S, _as_annotations, _embed_parts, _launch_sets, _open_engine, _read_chunks,
-                      _recordings, _torch, embed_annotated)
+from .dataset import (DIGITS_TIME, FRAMELENGTH_S, _as_annotations, _embed_parts, _launch_sets, _open_engine, _part_windows,
+                      _sources, _stored, _torch, embed_annotated)
 
 HIT_COLUMNS = ("query", "rank", "ident", "start", "end", "score")
 ANNOTATION_COLUMNS = ("ident", "start", "end", "label")
@@ -320,20 +320,19 @@ def _walk(dir_audio: str, engine, framehop_prop: float, chunklength: float, mess
     one set, hands its rows to a Searcher and returns (first id, windows per part); the rows are dropped before the next.
     ``recording_done(ident, chunk starts, windows per chunk)``, if given, is called after a recording's last set,
     ``recording_starts(ident, chunk starts)`` before its first.  ``annotations`` / ``only_annotated``: as embed_annotated
-    takes them (recordings the annotations do not mention are left out; annotated ones that do not exist are reported)."""
+    takes them (recordings the annotations do not mention are left out; annotated ones that do not exist are reported).
+    ``dir_audio`` may be an embedding store (``dataset._sources``): the parts are then handles on stored rows."""
     from .engine import hop_samples, patch_step
     framehop_s = FRAMELENGTH_S * framehop_prop
     hop, step = hop_samples(framehop_s), patch_step(framehop_s)
     chunklength = framing.round_chunklength(chunklength, FRAMELENGTH_S, DIGITS_TIME)
     index = _Index(framehop_s)
-    for path, ident in _recordings(dir_audio, {} if annotations is None else annotations, only_annotated, messages):
-        chunks = _read_chunks(engine, path, ident, len(index.idents), chunklength, messages)
-        if not chunks:
-            continue
+    for ident, chunks in _sources(dir_audio, engine, framehop_prop, chunklength, {} if annotations is None else annotations,
+                                  only_annotated, messages):
         if recording_starts is not None:
             recording_starts(ident, [c.start_s for c in chunks])
         parts = [c.pcm for c in chunks]
-        windows = [engine.num_windows(int(p.numel()), hop, step) for p in parts]
+        windows = [_part_windows(engine, p, hop, step) for p in parts]
         first_id, all_counts = None, []
         for a, b in _launch_sets(parts, windows):
             first, counts = feed(parts[a:b], hop, step)
@@ -371,7 +370,10 @@ def search_recordings(dir_audio: str, queries, *, k: int = 100, metric: str = "c
 
 def _logit_parts(engine, parts, hop: int, step: int):
     """``dataset._embed_parts`` for logits: one launch set, final (a set whose activations left the f16 range is repeated
-    with exact-f32 products)."""
+    with exact-f32 products).  Parts of an embedding store: their stored rows through ``engine.score_rows``, the heads alone."""
+    if _stored(parts):
+        rows, counts = _embed_parts(engine, parts, hop, step)
+        return engine.score_rows(rows), counts
     from .engine import LaunchVerdict
     f16 = engine._mode != "f32"
     verdict = LaunchVerdict(engine._stream()) if f16 else None
