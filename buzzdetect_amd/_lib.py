@@ -459,6 +459,25 @@ ROWS_PROTOTYPES = {
     "bd_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
+SUGGEST_ABI_VERSION = 1
+SUGGEST_MAX_MEMBERS = 64
+SUGGEST_MAX_WIDTH = 64
+SUGGEST_MAX_POOL = 1024
+SUGGEST_STRATEGIES = {"entropy": 0, "margin": 1, "bald": 2}
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_suggest.h
+SUGGEST_PROTOTYPES = {
+    "bd_suggest_abi_version": (C.c_int, []),
+    "bd_suggest_acquire": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_suggest_acquire_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_int64]),
+    "bd_suggest_pick": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "bd_suggest_pick_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -494,7 +513,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ENSEMBLE_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
             + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()) \
-            + list(EVAL_PROTOTYPES.items()) + list(ROWS_PROTOTYPES.items()):
+            + list(EVAL_PROTOTYPES.items()) + list(ROWS_PROTOTYPES.items()) + list(SUGGEST_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -530,6 +549,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: eval ABI version {lib.bd_eval_abi_version()} != {EVAL_ABI_VERSION}; rebuild")
     if lib.bd_rows_abi_version() != ROWS_ABI_VERSION:
         raise RuntimeError(f"{path}: rows ABI version {lib.bd_rows_abi_version()} != {ROWS_ABI_VERSION}; rebuild")
+    if lib.bd_suggest_abi_version() != SUGGEST_ABI_VERSION:
+        raise RuntimeError(f"{path}: suggest ABI version {lib.bd_suggest_abi_version()} != {SUGGEST_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 
