@@ -478,6 +478,30 @@ SUGGEST_PROTOTYPES = {
                                        C.c_void_p]),
 }
 
+PITCH_ABI_VERSION = 1
+PITCH_MAX_SELECTED = 1 << 20
+PITCH_MAX_STEP = 1 << 24
+PITCH_WINDOW = 15360
+PITCH_FRAMES = 29
+PITCH_FRAME = 1024
+PITCH_INTEGRATION = 512
+PITCH_MAX_LAG = 511
+
+
+class bd_pitch_params(C.Structure):
+    _fields_ = [("lag_lo", C.c_int32), ("lag_hi", C.c_int32), ("pick_ratio", C.c_float), ("clarity_min", C.c_float),
+                ("min_voiced", C.c_int32), ("rate_hz", C.c_float)]
+
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_pitch.h
+PITCH_PROTOTYPES = {
+    "bd_pitch_abi_version": (C.c_int, []),
+    "bd_pitch_windows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "bd_pitch_windows_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -513,7 +537,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             + list(HEAD_PROTOTYPES.items()) + list(HEADSET_PROTOTYPES.items()) + list(ENSEMBLE_PROTOTYPES.items()) + list(ANYRATE_PROTOTYPES.items()) + list(TRAIN_PROTOTYPES.items()) \
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
             + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()) \
-            + list(EVAL_PROTOTYPES.items()) + list(ROWS_PROTOTYPES.items()) + list(SUGGEST_PROTOTYPES.items()):
+            + list(EVAL_PROTOTYPES.items()) + list(ROWS_PROTOTYPES.items()) + list(SUGGEST_PROTOTYPES.items()) \
+            + list(PITCH_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -551,6 +576,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: rows ABI version {lib.bd_rows_abi_version()} != {ROWS_ABI_VERSION}; rebuild")
     if lib.bd_suggest_abi_version() != SUGGEST_ABI_VERSION:
         raise RuntimeError(f"{path}: suggest ABI version {lib.bd_suggest_abi_version()} != {SUGGEST_ABI_VERSION}; rebuild")
+    if lib.bd_pitch_abi_version() != PITCH_ABI_VERSION:
+        raise RuntimeError(f"{path}: pitch ABI version {lib.bd_pitch_abi_version()} != {PITCH_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 
