@@ -502,6 +502,46 @@ PITCH_PROTOTYPES = {
                                         C.c_void_p]),
 }
 
+HEALTH_ABI_VERSION = 1
+HEALTH_S16 = 0
+HEALTH_F32 = 1
+HEALTH_MAX_CHANNELS = 8
+HEALTH_SEGMENT = 4096
+HEALTH_MAX_SEGMENTS = 1 << 24
+HEALTH_MAX_RUN = 1 << 24
+HEALTH_SUM_DEPTH = 24
+HEALTH_FRAME = 1024
+HEALTH_HOP = 512
+HEALTH_BINS = 513
+HEALTH_SEGMENT_FRAMES = 64
+HEALTH_MAX_BANDS = 64
+HEALTH_TABLE_FLOATS = 2048
+
+
+class bd_health_level_params(C.Structure):
+    _fields_ = [("clip_hi", C.c_float), ("clip_lo", C.c_float), ("clip_run", C.c_int32), ("flat_run", C.c_int32)]
+
+
+class bd_health_record(C.Structure):
+    _fields_ = [("n", C.c_int32), ("nonfinite", C.c_int32), ("peak", C.c_float), ("sum", C.c_float), ("sumsq", C.c_float),
+                ("n_full", C.c_int32), ("clipped", C.c_int32), ("clip_runs", C.c_int32), ("flat", C.c_int32), ("flat_runs", C.c_int32)]
+
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_health.h
+HEALTH_PROTOTYPES = {
+    "bd_health_abi_version": (C.c_int, []),
+    "bd_health_check_cover": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_char_p]),
+    "bd_health_levels_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "bd_health_levels": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_health_levels_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bd_health_tables": (C.c_int, [C.c_void_p]),
+    "bd_health_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "bd_health_spectrum_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -538,7 +578,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
             + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()) \
             + list(EVAL_PROTOTYPES.items()) + list(ROWS_PROTOTYPES.items()) + list(SUGGEST_PROTOTYPES.items()) \
-            + list(PITCH_PROTOTYPES.items()):
+            + list(PITCH_PROTOTYPES.items()) + list(HEALTH_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -578,6 +618,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: suggest ABI version {lib.bd_suggest_abi_version()} != {SUGGEST_ABI_VERSION}; rebuild")
     if lib.bd_pitch_abi_version() != PITCH_ABI_VERSION:
         raise RuntimeError(f"{path}: pitch ABI version {lib.bd_pitch_abi_version()} != {PITCH_ABI_VERSION}; rebuild")
+    if lib.bd_health_abi_version() != HEALTH_ABI_VERSION:
+        raise RuntimeError(f"{path}: health ABI version {lib.bd_health_abi_version()} != {HEALTH_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

@@ -216,8 +216,9 @@ def _recordings(dir_audio: str, annotations: Annotations, only_annotated: bool, 
     return out
 
 
-def _read_chunks(engine, path: str, ident: str, group: int, chunklength: float, messages: List[str]) -> List[_Chunk]:
-    """One recording as the feeder and the analyzers bring it to the CNN: analyze's chunks, each at 16 kHz mono on the device."""
+def _read_chunks(engine, path: str, ident: str, group: int, chunklength: float, messages: List[str], on_raw=None) -> List[_Chunk]:
+    """One recording as the feeder and the analyzers bring it to the CNN: analyze's chunks, each at 16 kHz mono on the device.
+    ``on_raw(raw, rate, first_frame)``, if given, sees every chunk's native samples on the device before they are resampled."""
     from .flacio import open_track
     from .wavio import WavFormatError
     try:
@@ -240,6 +241,8 @@ def _read_chunks(engine, path: str, ident: str, group: int, chunklength: float, 
             got = int(raw.shape[0])
             if got == 0:
                 break
+            if on_raw is not None:
+                on_raw(raw, rate, a)
             if raw.dtype != _torch().float32 or rate != 16000 or track.channels > 1:
                 pcm = engine.resample(raw, rate, 16000)          # also int16 -> float32 and the channel mean
             else:
