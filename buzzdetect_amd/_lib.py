@@ -542,6 +542,29 @@ HEALTH_PROTOTYPES = {
                                           C.c_void_p]),
 }
 
+PCA_ABI_VERSION = 1
+PCA_DIM = 1024
+PCA_MAX_COMPONENTS = 64
+PCA_MAX_ROWS = 1 << 18
+PCA_SLICE = 1024
+PCA_SUM_SLICE = 256
+PCA_TILES = 528                     # 32 x 32 tiles of the Gram matrix's upper triangle, the diagonal included
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_pca.h
+PCA_PROTOTYPES = {
+    "bd_pca_abi_version": (C.c_int, []),
+    "bd_pca_sums": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_pca_sums_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_pca_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "bd_pca_gram": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                              C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_pca_gram_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "bd_pca_project": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    "bd_pca_project_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -578,7 +601,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
             + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()) \
             + list(EVAL_PROTOTYPES.items()) + list(ROWS_PROTOTYPES.items()) + list(SUGGEST_PROTOTYPES.items()) \
-            + list(PITCH_PROTOTYPES.items()) + list(HEALTH_PROTOTYPES.items()):
+            + list(PITCH_PROTOTYPES.items()) + list(HEALTH_PROTOTYPES.items()) + list(PCA_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -620,6 +643,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: pitch ABI version {lib.bd_pitch_abi_version()} != {PITCH_ABI_VERSION}; rebuild")
     if lib.bd_health_abi_version() != HEALTH_ABI_VERSION:
         raise RuntimeError(f"{path}: health ABI version {lib.bd_health_abi_version()} != {HEALTH_ABI_VERSION}; rebuild")
+    if lib.bd_pca_abi_version() != PCA_ABI_VERSION:
+        raise RuntimeError(f"{path}: PCA ABI version {lib.bd_pca_abi_version()} != {PCA_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 
