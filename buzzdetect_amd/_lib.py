@@ -565,6 +565,42 @@ PCA_PROTOTYPES = {
                                       C.c_void_p, C.c_void_p]),
 }
 
+KNN_ABI_VERSION = 1
+KNN_DIM = 1024
+KNN_MAX_K = 64
+KNN_MAX_ROWS = 1 << 22
+KNN_METRICS = {"dot": 0, "cosine": 1}
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_knn.h
+KNN_PROTOTYPES = {
+    "bd_knn_abi_version": (C.c_int, []),
+    "bd_knn_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "bd_knn_update": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_knn_update_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                     C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
+    "bd_knn_decode_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+}
+
+PROPAGATE_ABI_VERSION = 1
+PROPAGATE_MAX_CLASSES = 64
+PROPAGATE_MAX_POWER = 16
+PROPAGATE_MAX_ROWS = 1 << 24
+PROPAGATE_SLICE = 256
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_propagate.h
+PROPAGATE_PROTOTYPES = {
+    "bd_propagate_abi_version": (C.c_int, []),
+    "bd_propagate_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_propagate_weights_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_propagate_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_propagate_step_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bd_propagate_readout": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_propagate_readout_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -601,7 +637,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             + list(BANK_PROTOTYPES.items()) + list(STACKBANK_PROTOTYPES.items()) + list(MIX_PROTOTYPES.items()) \
             + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()) \
             + list(EVAL_PROTOTYPES.items()) + list(ROWS_PROTOTYPES.items()) + list(SUGGEST_PROTOTYPES.items()) \
-            + list(PITCH_PROTOTYPES.items()) + list(HEALTH_PROTOTYPES.items()) + list(PCA_PROTOTYPES.items()):
+            + list(PITCH_PROTOTYPES.items()) + list(HEALTH_PROTOTYPES.items()) + list(PCA_PROTOTYPES.items()) \
+            + list(KNN_PROTOTYPES.items()) + list(PROPAGATE_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -645,6 +682,10 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: health ABI version {lib.bd_health_abi_version()} != {HEALTH_ABI_VERSION}; rebuild")
     if lib.bd_pca_abi_version() != PCA_ABI_VERSION:
         raise RuntimeError(f"{path}: PCA ABI version {lib.bd_pca_abi_version()} != {PCA_ABI_VERSION}; rebuild")
+    if lib.bd_knn_abi_version() != KNN_ABI_VERSION:
+        raise RuntimeError(f"{path}: kNN ABI version {lib.bd_knn_abi_version()} != {KNN_ABI_VERSION}; rebuild")
+    if lib.bd_propagate_abi_version() != PROPAGATE_ABI_VERSION:
+        raise RuntimeError(f"{path}: propagation ABI version {lib.bd_propagate_abi_version()} != {PROPAGATE_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 
