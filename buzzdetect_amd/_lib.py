@@ -601,6 +601,32 @@ PROPAGATE_PROTOTYPES = {
     "bd_propagate_readout_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+TSNE_ABI_VERSION = 1
+TSNE_MAX_ROWS = 1 << 20
+TSNE_MAX_K = 64
+TSNE_SLICE = 2048
+TSNE_ROWS_PER_BLOCK = 256
+TSNE_BISECTIONS = 64
+
+# name -> (restype, argtypes); one entry per prototype in include/buzzdetect_tsne.h
+TSNE_PROTOTYPES = {
+    "bd_tsne_abi_version": (C.c_int, []),
+    "bd_tsne_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "bd_tsne_affinities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_tsne_affinities_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "bd_tsne_attract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bd_tsne_attract_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bd_tsne_repulse": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_tsne_repulse_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bd_tsne_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
+                                 C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bd_tsne_update_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
+                                      C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "bd_tsne_kl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_int64, C.c_void_p]),
+    "bd_tsne_kl_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -638,7 +664,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
             + list(SEARCH_PROTOTYPES.items()) + list(CLUSTER_PROTOTYPES.items()) + list(CALLS_PROTOTYPES.items()) \
             + list(EVAL_PROTOTYPES.items()) + list(ROWS_PROTOTYPES.items()) + list(SUGGEST_PROTOTYPES.items()) \
             + list(PITCH_PROTOTYPES.items()) + list(HEALTH_PROTOTYPES.items()) + list(PCA_PROTOTYPES.items()) \
-            + list(KNN_PROTOTYPES.items()) + list(PROPAGATE_PROTOTYPES.items()):
+            + list(KNN_PROTOTYPES.items()) + list(PROPAGATE_PROTOTYPES.items()) + list(TSNE_PROTOTYPES.items()):
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -686,6 +712,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path}: kNN ABI version {lib.bd_knn_abi_version()} != {KNN_ABI_VERSION}; rebuild")
     if lib.bd_propagate_abi_version() != PROPAGATE_ABI_VERSION:
         raise RuntimeError(f"{path}: propagation ABI version {lib.bd_propagate_abi_version()} != {PROPAGATE_ABI_VERSION}; rebuild")
+    if lib.bd_tsne_abi_version() != TSNE_ABI_VERSION:
+        raise RuntimeError(f"{path}: t-SNE ABI version {lib.bd_tsne_abi_version()} != {TSNE_ABI_VERSION}; rebuild")
     _lib = lib
     return lib
 

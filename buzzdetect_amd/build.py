@@ -18,7 +18,7 @@ import tempfile
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_NAME = "libbuzzdetect_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ("engine.hip", "engine_pass.hip", "weights_fold.hip", "resample_host.hip", "stager.hip", "frontend.hip", "resample.hip", "sepchip.hip", "sepchipf32.hip", "sepmid.hip", "sepmidf32.hip", "septail.hip", "stemreg.hip", "stemregf32.hip", "l4regf32.hip", "cnn.hip", "sepws.hip", "l4window.hip", "stem3.hip", "rowfmt.hip", "flac.hip", "pcmcodec.hip", "headmlp.hip", "anyrate.hip", "headtrain.hip", "headbank.hip", "stackbank.hip", "mixaug.hip", "headset.hip", "ensemble.hip", "simsearch.hip", "cluster.hip", "calls.hip", "evalsweep.hip", "rowcodec.hip", "suggest.hip", "pitch.hip", "health.hip", "pca.hip", "knn.hip", "propagate.hip")
+SOURCES = ("engine.hip", "engine_pass.hip", "weights_fold.hip", "resample_host.hip", "stager.hip", "frontend.hip", "resample.hip", "sepchip.hip", "sepchipf32.hip", "sepmid.hip", "sepmidf32.hip", "septail.hip", "stemreg.hip", "stemregf32.hip", "l4regf32.hip", "cnn.hip", "sepws.hip", "l4window.hip", "stem3.hip", "rowfmt.hip", "flac.hip", "pcmcodec.hip", "headmlp.hip", "anyrate.hip", "headtrain.hip", "headbank.hip", "stackbank.hip", "mixaug.hip", "headset.hip", "ensemble.hip", "simsearch.hip", "cluster.hip", "calls.hip", "evalsweep.hip", "rowcodec.hip", "suggest.hip", "pitch.hip", "health.hip", "pca.hip", "knn.hip", "propagate.hip", "tsne.hip")
 # extra compiler flags of single files (part of the source hash below, like the sources themselves)
 FILE_FLAGS = {
     # sep_chip_kernel lives at the 256-register limit of two waves per SIMD: the default machine scheduler spills 4-28 of its
@@ -28,7 +28,7 @@ FILE_FLAGS = {
     "sepchipf32.hip": ("-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"),
     "sepmidf32.hip": ("-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"),
 }
-HEADERS = ("bd_internal.h", "bd_error.h", "engine_state.h", "bd_device.h", "headtrain_device.h", "headtrain_host.h", "headtrain_stack.h", "dense_device.h", "ensemble_device.h", "simsearch_device.h", "cluster_device.h", "calls_device.h", "evalsweep_device.h", "rowcodec_device.h", "suggest_device.h", "pitch_device.h", "health_device.h", "pca_device.h", "knn_device.h", "propagate_device.h", os.path.join("..", "..", "include", "buzzdetect_hip.h"),
+HEADERS = ("bd_internal.h", "bd_error.h", "engine_state.h", "bd_device.h", "headtrain_device.h", "headtrain_host.h", "headtrain_stack.h", "dense_device.h", "ensemble_device.h", "simsearch_device.h", "cluster_device.h", "calls_device.h", "evalsweep_device.h", "rowcodec_device.h", "suggest_device.h", "pitch_device.h", "health_device.h", "pca_device.h", "knn_device.h", "propagate_device.h", "tsne_device.h", os.path.join("..", "..", "include", "buzzdetect_hip.h"),
            os.path.join("..", "..", "include", "buzzdetect_flac.h"), os.path.join("..", "..", "include", "buzzdetect_pcm.h"),
            os.path.join("..", "..", "include", "buzzdetect_head.h"),
            os.path.join("..", "..", "include", "buzzdetect_headset.h"),
@@ -48,7 +48,8 @@ HEADERS = ("bd_internal.h", "bd_error.h", "engine_state.h", "bd_device.h", "head
            os.path.join("..", "..", "include", "buzzdetect_health.h"),
            os.path.join("..", "..", "include", "buzzdetect_pca.h"),
            os.path.join("..", "..", "include", "buzzdetect_knn.h"),
-           os.path.join("..", "..", "include", "buzzdetect_propagate.h"))
+           os.path.join("..", "..", "include", "buzzdetect_propagate.h"),
+           os.path.join("..", "..", "include", "buzzdetect_tsne.h"))
 ARCH = "gfx950"
 
 
